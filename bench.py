@@ -2,24 +2,40 @@
 """Benchmark of the APPNP propagation hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload products-synth]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one full propagation call -- K=10 fused SpMM+AXPBY iterations over the whole
 graph (appnp_propagate, or the partitioned multi-GPU loop) -- on synthetic input that is
 resident in HBM before the timed region.  value = nodes * F * K * steps / time (whole job).
 
+A plain run does only what the headline figure needs: it draws the seeded input, builds the
+graph, runs --warmup steps, times exactly --steps steps (``ms_per_step`` = their wall time /
+their number), writes the outputs if asked to and prints the result line.  The roofline block
+of a plain line is arithmetic on the timed region alone.  --full adds what takes runs of its own:
+the CPU baseline, the parity of the timed Z_K against it, the line-rate probe before the timed
+region and the per-launch split after it (``cpu_baseline``, ``parity``, ``roofline.kernel_ms``,
+``roofline.box_line_rate``; --cpu-iters applies to it).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path left in its output buffer
+in the last step: ``DIR/Z.npy`` (N = 1) or ``DIR/Z_rank<r>.npy`` (each rank's block of the
+printed layout), float32.  Above DUMP_MAX_BYTES in all, a fixed seeded sample of the rows, in
+ascending order (``dump_rows``).  The input is seeded, so two builds run with the same
+arguments write the same rows of the same problem.
+
 N > 1 (launched by torch.distributed.run, one rank per GPU): the ranks form an R x C layout
 (ppnp_amd/dist.py): C feature slabs need no exchange, R row groups
 exchange their Z shards over RCCL every iteration.  --layout auto measures every candidate
 layout of ppnp_amd.dist.candidate_layouts with the full protocol (W warm-up steps, then exactly
-K timed steps bracketed by barrier + synchronize, max over ranks, parity of the result) and
-prints the fastest one whose parity holds.  The candidate without a data-path exchange (the
-column layout) is measured first, and every later candidate runs under a deadline
+K timed steps bracketed by barrier + synchronize, max over ranks; with --full, parity of the
+result) and prints the fastest one (--full: whose parity holds).  The candidate without a
+data-path exchange (the column layout) is measured first, and every later one under a deadline
 (--candidate-timeout): if an exchange stalls, the RCCL communicators are aborted, rank 0
 prints the best line measured so far, and every rank exits -- the scaling run always gets a
 line unless the exchange-free layout itself fails.  --run-budget bounds the whole run: no
 candidate starts with less than MIN_CANDIDATE_S of it left, and a running one is cut short.
 
-Extra JSON fields:
+Extra JSON fields (``box_line_rate``, ``kernel_ms``, ``cpu_baseline`` and ``parity`` with --full
+only; a plain line has null or no entry there):
   roofline      HBM roofline of the iteration's kernels on one rank: algorithmic bytes per
                 iteration B_iter = 4(rows+1) + 8 nnz(A_hat rows) + (n + 2 rows) F s (SURVEY.md
                 section 8(d), restricted to the rank's share) / the average iteration time,
@@ -88,6 +104,9 @@ PARITY_BCAST_MAX_BYTES = 4 << 30
 # The in-library line-rate probe run before the timed region (appnp_line_rate_probe): random
 # 128-B lines gathered from the bench's own H buffer, ~20 ms
 PROBE_LINES = 1 << 30
+# --dump-outputs: the most all ranks together write (float32), and the seed of the row sample
+DUMP_MAX_BYTES = 60_000_000
+DUMP_SEED = 0
 
 
 def parse(argv=None):
@@ -100,9 +119,16 @@ def parse(argv=None):
                    help="override the workload's storage dtype (non-headline variants)")
     p.add_argument("--features", type=int, default=None,
                    help="override the workload's feature width F (non-headline variants)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the "
+                        "parity of the timed Z_K against it, the line-rate probe and the "
+                        "per-launch split of the roofline block")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the output of the last one to DIR as .npy "
+                        "(float32; a fixed seeded sample of the rows above DUMP_MAX_BYTES)")
     p.add_argument("--cpu-iters", type=int, default=None,
-                   help="iterations of the CPU baseline sample (default K: its Z_K is then the "
-                        "parity reference of the GPU result; 0 disables it)")
+                   help="--full: iterations of the CPU baseline sample (default K: its Z_K is "
+                        "then the parity reference of the GPU result; 0 disables it)")
     p.add_argument("--layout", default="auto",
                    help="multi-GPU layout: auto | row | col | RxC (row groups x column groups)")
     p.add_argument("--emulate", default=None, metavar="P:r",
@@ -490,6 +516,35 @@ def time_steps(run, stream, steps, warmup, world, ctl):
     return wall, dev_ms, steps_ms
 
 
+def dump_rows(rows, width, world):
+    """--dump-outputs: which of the ``rows`` rows of a rank's [rows, width] output block are
+    written -- None for all of them, or, where the ``world`` blocks together would pass
+    DUMP_MAX_BYTES as float32, a sample drawn without replacement from
+    ``numpy.random.default_rng(DUMP_SEED)``, ascending: the same rows for the same shape."""
+    import numpy as np
+
+    keep = DUMP_MAX_BYTES // max(1, world) // max(1, 4 * width)
+    if rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+
+
+def sample_output(out, world):
+    """The float32 host array --dump-outputs writes for the output block ``out`` of one rank
+    (call it after the timed region's synchronize, before anything else runs the path)."""
+    rows = dump_rows(int(out.shape[0]), int(out.shape[1]), world)
+    if rows is not None:
+        out = out[torch.from_numpy(rows).to(out.device)]
+    return out.float().cpu().numpy()
+
+
+def write_output(directory, name, arr):
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def kernel_split(run, device, K, iteration_ms):
     """roofline.kernel_ms: the device time of every launch of ONE untimed propagation, run right
     after the timed region with the library's per-launch timer (appnp_kernel_timer_*: a HIP event
@@ -803,9 +858,10 @@ def main(argv=None):
 
     # the CPU leg: all K iterations by default, at N > 1 too (products-synth: ~11 s at 16
     # threads, once per run), so its Z_K is the parity reference of every line
-    cpu_iters = K if args.cpu_iters is None else args.cpu_iters
+    # -- with --full only: a plain run has no CPU leg and no parity
+    cpu_iters = (K if args.cpu_iters is None else args.cpu_iters) if args.full else 0
     adj_small = None
-    if n <= 20000 and rank == 0:  # the as-shipped PPNP leg of the CPU baseline needs A
+    if cpu_iters > 0 and n <= 20000 and rank == 0:  # the as-shipped PPNP leg needs A
         import numpy as np
         import scipy.sparse as sp
 
@@ -825,7 +881,9 @@ def main(argv=None):
     def box_line_rate():
         """roofline.box_line_rate: this GPU's random 128-B line rate right before the timed
         region (appnp_line_rate_probe on the bench's own H buffer, ~20 ms), so a line in a slow
-        timing state says so itself (VERDICT r3 #5; DESIGN.md 6)."""
+        timing state says so itself (VERDICT r3 #5; DESIGN.md 6).  With --full only."""
+        if not args.full:
+            return None
         try:
             from ppnp_amd.ops import line_rate_probe
 
@@ -847,7 +905,8 @@ def main(argv=None):
                       traffic=committed_traffic(tkey))
         rl["source_blocks"] = sb
         rl["traffic_key"] = tkey
-        rl["kernel_ms"] = kernel_split(runner.run, dev, K, avg_iter_ms)
+        # the per-launch split runs one more propagation: with --full only
+        rl["kernel_ms"] = kernel_split(runner.run, dev, K, avg_iter_ms) if args.full else None
         rl["box_line_rate"] = box["G_lines_s"] if box else None
         rl["box_line_probe"] = (dict(box, source="appnp_line_rate_probe (ppnp_amd/csrc/"
                                      "appnp_probe.hip): random 128-B lines of the H buffer, "
@@ -897,6 +956,8 @@ def main(argv=None):
         log(f"[bench] nnz_hat={graph.nnz_hat} build {t_build:.3f}s")
         box = box_line_rate()
         wall, dev_ms, steps_ms = time_steps(runner.run, stream, args.steps, args.warmup, 1, None)
+        if args.dump_outputs:  # the last timed step's Z_K, before anything else runs the path
+            write_output(args.dump_outputs, "Z", sample_output(runner.out, 1))
         res = result(runner, wall, dev_ms, steps_ms, "single", 0, box)
         res["config"]["nnz_a_hat"] = graph.nnz_hat
         if cpu_iters > 0:
@@ -916,7 +977,8 @@ def main(argv=None):
     # rank over the gloo control group; each rank then checks its block of the timed Z_K
     # against it (max over ranks).  Only with the CPU leg cut short (--cpu-iters < K) is the
     # reference a single-GPU appnp_propagate of the whole graph on every rank instead.  An
-    # emulated rank (no exchange: stale gathered rows) has no parity.
+    # emulated rank (no exchange: stale gathered rows) has no parity.  All of it with --full
+    # only: a plain run has no reference, and every candidate it times is eligible.
     nnz_total = None
     Zc = None
     if rank == 0:
@@ -949,7 +1011,7 @@ def main(argv=None):
             torch.distributed.broadcast(Zc, 0, group=ctl)
     use_oracle = use_oracle and Zc is not None
     Zref = None
-    if not use_oracle and not args.emulate:
+    if args.full and not use_oracle and not args.emulate:
         Gref = ppnp_amd.Graph.from_csr(indptr, indices, None, n, mode="sym", device=dev)
         Zref = ppnp_amd.propagate_forward(Gref, H, K, alpha)
         Gref.close()
@@ -963,6 +1025,7 @@ def main(argv=None):
         ref_name = "single-GPU appnp_propagate of the whole graph, per rank (max over ranks)"
 
     pipeline = {"auto": None, "on": True, "off": False}[args.pipeline]
+    dumps = {}  # --dump-outputs: candidate name -> this rank's sampled output block
 
     def measure(cand):
         layout, overlap, exchange = cand
@@ -985,6 +1048,8 @@ def main(argv=None):
                                      else "")
             if args.emulate:
                 par += f"-EMULATED-rank{args.emulate}"
+            if args.dump_outputs:  # this rank's block of the last timed step, kept on the host
+                dumps[par] = sample_output(runner.out, world)
             R = runner.layout.rows
             # the other row shards of this rank's column group land here every iteration
             exchange_in = ((R - 1) * runner.shard * runner.width * esz
@@ -1024,6 +1089,8 @@ def main(argv=None):
         res, _ = run_candidates(cands, measure, ctl, args.candidate_timeout, emit, cand_name,
                                 rank, world, exchanges=lambda c: c[0].rows > 1,
                                 budget_s=args.run_budget if world > 1 else 0.0)
+    if args.dump_outputs:  # every rank's block of the layout whose line is printed
+        write_output(args.dump_outputs, f"Z_rank{rank}", dumps[res["config"]["parallelism"]])
     if rank == 0:
         emit(res)
     if world > 1:

@@ -134,8 +134,10 @@ class SimpleEarlyStopping:
 def load_dataset(name):
     """Standardized LCC adjacency, attributes and labels from tests/golden/<name>.npz (the
     reference's own SparseGraph.standardize output, see tests/golden/make_golden.py)."""
-    path = os.path.join(ROOT, "tests", "golden", name + ".npz")
-    d = np.load(path, allow_pickle=False)
+    path = os.path.join(ROOT, "tests", "golden", name)
+    d = dict(np.load(path + ".npz", allow_pickle=False))
+    if os.path.exists(path + "_attr.npz"):  # a dataset kept in parts: the attribute matrix
+        d.update(np.load(path + "_attr.npz", allow_pickle=False))
     n = int(d["n"])
     adj = sp.csr_matrix((d["adj_data"], d["adj_indices"], d["adj_indptr"]), shape=(n, n))
     attr = sp.csr_matrix((d["attr_data"], d["attr_indices"], d["attr_indptr"]),

@@ -31,7 +31,14 @@ def pytest_unconfigure(config):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False))
+    """The arrays of fixture ``name``: <name>.npz and, where a dataset's arrays are kept in
+    several files so that each stays below 1 MiB (make_golden.py), its _attr and _ppnp parts."""
+    out = dict(np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False))
+    for part in ("_attr", "_ppnp"):
+        path = os.path.join(GOLDEN, name + part + ".npz")
+        if os.path.exists(path):
+            out.update(np.load(path, allow_pickle=False))
+    return out
 
 
 @pytest.fixture(scope="session")

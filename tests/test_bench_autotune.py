@@ -29,7 +29,7 @@ def _rendezvous():
     import tempfile
     import uuid
 
-    d = os.path.join(tempfile.gettempdir(), "ppnp_rdv")
+    d = os.path.join(tempfile.gettempdir(), f"ppnp_rdv_{os.getuid()}")  # one per user
     os.makedirs(d, exist_ok=True)
     return "file://" + os.path.join(d, uuid.uuid4().hex)
 

@@ -201,7 +201,8 @@ def test_emulated_rank_key_equals_real_rank_key(world):
 
     import torch.multiprocessing as mp
 
-    d = os.path.join(tempfile.gettempdir(), "ppnp_rdv")  # file:// rendezvous: no port race
+    # file:// rendezvous: no port race; a directory of this user's own
+    d = os.path.join(tempfile.gettempdir(), f"ppnp_rdv_{os.getuid()}")
     os.makedirs(d, exist_ok=True)
     init = "file://" + os.path.join(d, uuid.uuid4().hex)
     ctx = mp.get_context("spawn")
@@ -262,3 +263,28 @@ def test_kernel_split_summarises_launches(monkeypatch):
     assert k["main"]["launches"] == 4 and k["local"]["mean"] == pytest.approx(0.2)
     assert k["remote"]["mean"] == pytest.approx(0.8) and k["xchg"]["launches"] == 2
     assert k["sum_of_kernels"] == pytest.approx((0.3 + 2 * 1.1) / 2)
+
+
+def test_plain_run_options_and_output_sample(tmp_path):
+    """--full and --dump-outputs are off by default.  The dumped sample: every row of a block
+    that fits, otherwise the same ascending, duplicate-free rows on every call, sized so that
+    all ranks together stay within DUMP_MAX_BYTES as float32; the written file is float32."""
+    import numpy as np
+    import torch
+
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    assert bench.DUMP_MAX_BYTES <= 64_000_000
+    assert bench.dump_rows(1000, 100, 1) is None
+    for rows, width, world in ((N, 100, 1), (N, 13, 8), (N // 8 + 1, 100, 8)):
+        r = bench.dump_rows(rows, width, world)
+        assert np.array_equal(r, bench.dump_rows(rows, width, world))
+        assert r.min() >= 0 and r.max() < rows and np.all(np.diff(r) > 0)
+        row = width * 4 * world  # float32 bytes of one sampled row over all ranks
+        assert (len(r) + 1) * row > bench.DUMP_MAX_BYTES >= len(r) * row
+    Z = torch.arange(12, dtype=torch.bfloat16).reshape(4, 3)
+    bench.write_output(str(tmp_path / "out"), "Z", bench.sample_output(Z, 1))
+    got = np.load(tmp_path / "out" / "Z.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, Z.float().numpy())

@@ -317,7 +317,7 @@ def test_bench_two_ranks_autotune_and_parity():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "arxiv-synth",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     proc = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=150)
     assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
     res = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][-1])
@@ -339,7 +339,7 @@ def test_bench_eight_ranks_every_candidate():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
            os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "arxiv-synth",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     proc = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
     res = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][-1])
@@ -365,7 +365,7 @@ def test_bench_rccl_refused_still_prints_the_column_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "arxiv-synth",
-           "--steps", "2", "--warmup", "1", "--candidate-timeout", "120"]
+           "--steps", "2", "--warmup", "1", "--full", "--candidate-timeout", "120"]
     proc = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
     res = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][-1])

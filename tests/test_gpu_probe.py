@@ -45,6 +45,43 @@ def test_bench_build_info_matches_the_tree():
     assert info["match"], info
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_output(tmp_path, capsys):
+    """A plain bench run (arxiv-synth: 87 MB of Z_K, so the dump is the row sample) times
+    exactly --steps steps, carries none of the --full legs, and --dump-outputs writes the sampled
+    rows of the timed Z_K: the same bits from a second run with the same arguments, and the
+    library's propagation of the same seeded input within the bench's own parity bar."""
+    import json
+
+    import numpy as np
+
+    import bench
+    import ppnp_amd
+    from ppnp_amd import synth
+
+    n, _, F, K, alpha, dtype = synth.CONFIGS["arxiv-synth"]
+    argv = ["--gpus", "1", "--workload", "arxiv-synth", "--steps", "3", "--warmup", "1"]
+    res = bench.main(argv + ["--dump-outputs", str(tmp_path / "a")])
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["ms_per_step"] == res["ms_per_step"] > 0 and line["steps"] == 3
+    assert line["value"] == pytest.approx(n * F * K / (line["ms_per_step"] * 1e-3))
+    assert line["unit"] == "node-feats/s" and line["higher_is_better"] and line["dtype"] == "f32"
+    assert "cpu_baseline" not in line and "parity" not in line
+    assert line["roofline"]["kernel_ms"] is None and line["roofline"]["box_line_rate"] is None
+    assert line["roofline"]["achieved"] > 0
+    rows = bench.dump_rows(n, F, 1)
+    Za = np.load(tmp_path / "a" / "Z.npy")
+    assert Za.dtype == np.float32 and Za.shape == (len(rows), F)
+    assert Za.nbytes <= bench.DUMP_MAX_BYTES < n * F * 4
+    bench.main(argv + ["--dump-outputs", str(tmp_path / "b")])
+    assert np.array_equal(Za, np.load(tmp_path / "b" / "Z.npy"))
+    indptr, indices = synth.graph_for("arxiv-synth", device=DEV)
+    g = ppnp_amd.Graph.from_csr(indptr, indices, None, n, mode="sym", device=DEV, features=F,
+                                dtype=dtype)
+    Z = ppnp_amd.propagate_forward(g, synth.features(n, F, dtype=dtype, device=DEV), K, alpha)
+    ref = Z.float().cpu().numpy()[rows]
+    assert np.abs(Za - ref).max() <= 1e-5 * np.abs(ref).max() + 1e-6
+
+
 def _split_graph(n=200_000, m=2_000_000, F=100):
     import ppnp_amd
     from ppnp_amd import synth

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """One row per bench line: the iteration time of the timed region beside roofline.kernel_ms (the
 per-launch split of one untimed propagation, appnp_kernel_timer_*) and the box's line rate.
+Lines of ``bench.py --full`` carry both; a plain line prints "-" / nan there.
 
     python tools/kernel_split_table.py <label>=<bench log or json> ...
 """

@@ -7,7 +7,7 @@ B="python bench.py --steps 5 --warmup 2 --cpu-iters 0"
 TR="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1 --master-port 29517"
 G="PPNP_DIST_BACKEND=gloo $TR"
 tools/gpu_session.sh \
- "bench_default::400::python bench.py" \
+ "bench_default::400::python bench.py --full" \
  "prof_stats::300::rocprofv3 --kernel-trace --stats -d gpurun_out/prof_stats -o run --output-format csv -- $B" \
  "pmc_fetch::300::rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run --output-format csv -- $B" \
  "pmc_write::300::rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write -o run --output-format csv -- $B" \
@@ -33,5 +33,5 @@ tools/gpu_session.sh \
  "w_powerlaw::200::$B --workload products-powerlaw" \
  "w_local::200::$B --workload products-local" \
  "w_bf16::200::$B --dtype bf16" \
- "dist2_auto::300::$G --nproc-per-node 2 bench.py --gpus 2 --steps 3 --warmup 1" \
- "dist4_auto::300::$G --nproc-per-node 4 bench.py --gpus 4 --steps 3 --warmup 1 --workload arxiv-synth"
+ "dist2_auto::300::$G --nproc-per-node 2 bench.py --gpus 2 --steps 3 --warmup 1 --full" \
+ "dist4_auto::300::$G --nproc-per-node 4 bench.py --gpus 4 --steps 3 --warmup 1 --workload arxiv-synth --full"

@@ -6,7 +6,7 @@
 set -u
 B="python bench.py --steps 5 --warmup 2 --cpu-iters 0"
 tools/gpu_session.sh \
- "bench_default::400::python bench.py" \
+ "bench_default::400::python bench.py --full" \
  "prof_stats::300::rocprofv3 --kernel-trace --stats -d gpurun_out/prof_stats -o run --output-format csv -- $B" \
  "pmc_fetch::300::timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run --output-format csv -- $B" \
  "pmc_write::300::timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write -o run --output-format csv -- $B" \
