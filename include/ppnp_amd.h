@@ -45,7 +45,10 @@ extern "C" {
  * workspace than version 1 asked for); the pipelined row steps (appnp_graph_shard_offsets,
  * appnp_step_shards, appnp_step_split_shards, appnp_dist_set_broadcast); the per-launch timer
  * brackets each launch (start and end events) and has the kinds APPNP_KT_LOCAL / _REMOTE /
- * _XCHG; appnp_tuning_overrides / appnp_tuning_names. */
+ * _XCHG; appnp_tuning_overrides / appnp_tuning_names.
+ * Added since, backward compatible (the version stays 2): the exact PPNP solver
+ * appnp_solve_iterations, appnp_solve_weights, appnp_solve, appnp_solve_bwd and
+ * appnp_plan_create_solve. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -244,6 +247,51 @@ int appnp_propagate_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, voi
                         uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * Exact PPNP: Z = Pi H with Pi = alpha (I - (1-alpha) A_hat)^-1 (helpers.py:68-71 compute_ppr,
+ * model.py:63), to a stated tolerance, without the dense inverse.  The fixed point of
+ * Z = (1-alpha) A_hat Z + alpha H is reached by Chebyshev semi-iteration instead of the plain
+ * series of appnp_propagate.  On an undirected graph ('sym' or 'rw') the spectrum of
+ * (1-alpha) A_hat is real and lies in [-rho, rho], rho = 1 - alpha, so
+ *
+ *   Z_0 = H,   Z_{k+1} = w_{k+1} ((1-alpha) A_hat Z_k + alpha H) + (1 - w_{k+1}) Z_{k-1},
+ *   w_1 = 1,   w_2 = 1 / (1 - rho^2 / 2),   w_{k+1} = 1 / (1 - rho^2 w_k / 4)
+ *
+ * shrinks the error by sigma = rho / (1 + sqrt(1 - rho^2)) per step (0.627 at alpha = 0.1,
+ * against 0.9 for the plain series): after m steps it is at most 2 sigma^m / (1 + sigma^2m) of
+ * the initial one.
+ *
+ * appnp_solve_iterations  *iters = the smallest m >= 1 with 2 sigma^m / (1 + sigma^2m) <= tol
+ *                         (alpha = 0.1: tol 1e-5 / 1e-6 / 1e-7 -> 27 / 32 / 36).  Host only.
+ *                         APPNP_EINVAL unless 0 < alpha <= 1 and 0 < tol < 1; APPNP_ERANGE when
+ *                         alpha is so small that no count below 2^20 reaches tol.
+ * appnp_solve_weights     omega[0 .. iters) = w_1 .. w_iters in fp64.  Host only.
+ * appnp_solve             `iters` steps from Z_0 = H, the last one into Z: one launch of the
+ *                         fused SpMM kernel per step (timed as APPNP_KT_STEP), whose epilogue
+ *                         reads one extra row, Z_{k-1}.  The count is fixed a priori, so no
+ *                         residual is read back: stream-ordered, no allocation, graph-capturable,
+ *                         like appnp_propagate.  ws: appnp_workspace_bytes() bytes.
+ * appnp_solve_bwd         dH = Pi^T dZ: the same solve on A_hat^T (A_hat itself for 'sym', the
+ *                         transpose built with APPNP_GRAPH_TRANSPOSE for 'rw'; APPNP_ENOTSUP
+ *                         without it).  This is the gradient of the CONVERGED operator H -> Pi H,
+ *                         exact to the same tolerance -- not the adjoint of a loop truncated at
+ *                         `iters` steps.
+ * Limits: a full graph; H != Z; fp32 only (APPNP_ENOTSUP for bf16); an undirected graph only
+ * (APPNP_ENOTSUP when the graph's symmetric flag is 0: a directed A_hat has a complex spectrum
+ * and the recurrence may diverge); no dropout (a mask that changes per step has no fixed point).
+ * Rows are always gathered whole: the source-blocked remainder pass is not used, also on a graph
+ * that has the copy, and appnp_graph_source_block_layout's launch count does not move.
+ * Arguments are validated before any device call.
+ */
+int appnp_solve_iterations(float alpha, float tol, int* iters);
+int appnp_solve_weights(float alpha, int iters, double* omega);
+int appnp_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
+                int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
+                void* stream);
+int appnp_solve_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, void* dH, int64_t ld_dh,
+                    int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
+                    void* stream);
+
+/*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]
  *                                                   + alpha H[i-row_lo],  i in [row_lo,row_hi)
  *   Zin: all n rows (global row index), Zout/H: the held rows only.
@@ -344,6 +392,10 @@ typedef struct appnp_plan appnp_plan;
 int appnp_plan_create(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
                       int64_t f, int dtype, int K, float alpha, float p_drop, uint64_t seed,
                       void* ws, size_t ws_bytes, appnp_plan** out);
+/* The same for appnp_solve: its `iters` launches (a linear chain) captured into a plan. */
+int appnp_plan_create_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z,
+                            int64_t ld_z, int64_t f, int dtype, int iters, float alpha, void* ws,
+                            size_t ws_bytes, appnp_plan** out);
 int appnp_plan_launch(const appnp_plan* p, void* stream);
 void appnp_plan_destroy(appnp_plan* p);
 

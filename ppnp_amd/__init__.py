@@ -8,8 +8,8 @@ model.py:63, as hand-written HIP kernels behind the C ABI in include/ppnp_amd.h.
 from . import _lib
 from .graph import Graph
 from .model import APPNP, PPNP, CustomLinear
-from .ops import (propagate, propagate_backward, propagate_forward, split_copy, step,
-                  step_split)
+from .ops import (SolvePlan, propagate, propagate_backward, propagate_forward, solve,
+                  solve_backward, solve_forward, solve_iterations, split_copy, step, step_split)
 from .sparse import SparseFeatures, sparse_linear
 
 __all__ = [
@@ -20,6 +20,11 @@ __all__ = [
     "propagate",
     "propagate_forward",
     "propagate_backward",
+    "solve",
+    "solve_forward",
+    "solve_backward",
+    "solve_iterations",
+    "SolvePlan",
     "step",
     "step_split",
     "split_copy",

@@ -88,6 +88,14 @@ _SIGS = {
         [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _u64, _vp, _sz,
          C.POINTER(_vp)],
     ),
+    "appnp_solve_iterations": (_i32, [_f32, _f32, C.POINTER(_i32)]),
+    "appnp_solve_weights": (_i32, [_f32, _i32, C.POINTER(C.c_double)]),
+    "appnp_solve": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, _vp]),
+    "appnp_solve_bwd": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, _vp]),
+    "appnp_plan_create_solve": (
+        _i32,
+        [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, C.POINTER(_vp)],
+    ),
     "appnp_plan_launch": (_i32, [_vp, _vp]),
     "appnp_plan_destroy": (None, [_vp]),
     "appnp_dist_create": (

@@ -689,6 +689,148 @@ int appnp_propagate_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, voi
   return APPNP_OK;
 }
 
+// ---- exact PPNP: Chebyshev semi-iteration on Z = (1-alpha) A_hat Z + alpha H ---------------
+
+namespace {
+
+constexpr int kSolveMaxIters = 1 << 20;
+
+inline bool valid_solve_alpha(float alpha) { return alpha > 0.0f && alpha <= 1.0f; }
+
+// w_{k+1} from w_k (k >= 1 steps done): w_1 = 1, w_2 = 1 / (1 - rho^2 / 2), then the recurrence
+inline double next_omega(double rho, int k, double w) {
+  return k == 0 ? 1.0 : k == 1 ? 1.0 / (1.0 - 0.5 * rho * rho) : 1.0 / (1.0 - 0.25 * rho * rho * w);
+}
+
+// `iters` steps from Z_0 = H on the CSR in `a`, the last into Z.  Step 1 is the plain forward
+// step (w_1 = 1), step 2 reads Z_0 = H as its Z_{k-1}; from step 3 on Z_{k-1} sits in the
+// workspace buffer the step overwrites (step k writes buffer (k-1) % 2, which holds Z_{k-2}), so
+// two buffers carry the three-term recurrence.
+int solve_loop(StepArgs a, const void* H, int64_t ld_h, void* Z, int64_t ld_z, int64_t f,
+               int iters, float alpha, void* ws, size_t ws_bytes, hipStream_t s) {
+  const int64_t n = a.n_rows;
+  const int64_t ld_w = line_ld(f, APPNP_F32);
+  const int64_t buf = n * ld_w * 4;
+  const int nbuf = iters >= 3 ? 2 : (iters == 2 ? 1 : 0);
+  if (nbuf > 0) {
+    if (!ws) return APPNP_EINVAL;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+    const uintptr_t aligned = (base + 255) & ~uintptr_t(255);
+    if (ws_bytes < (size_t)(nbuf * buf) + (aligned - base)) return APPNP_EINVAL;
+    ws = reinterpret_cast<void*>(aligned);
+  }
+  void* w[2] = {nbuf >= 1 ? ws : nullptr, nbuf == 2 ? static_cast<char*>(ws) + buf : nullptr};
+  const int64_t lds[3] = {ld_h, ld_z, ld_w};
+  const void* ptrs[4] = {H, Z, w[0], w[1]};
+  const int V = appnp::pick_vec(APPNP_F32, f, lds, 3, ptrs, 4);
+  a.h = H;
+  a.ld_h = ld_h;
+  const double rho = 1.0 - (double)alpha;
+  double omega = 1.0;
+  const void* src = H;
+  int64_t ld_src = ld_h;
+  for (int k = 1; k <= iters; ++k) {
+    omega = next_omega(rho, k - 1, omega);
+    const bool last = k == iters;
+    void* dst = last ? Z : w[(k - 1) & 1];
+    const int64_t ld_dst = last ? ld_z : ld_w;
+    a.zin = src;
+    a.ld_in = ld_src;
+    a.out = dst;
+    a.ld_out = ld_dst;
+    int epi = appnp::EPI_FWD;
+    if (k >= 2) {
+      epi = appnp::EPI_CHEB;
+      a.aux = k == 2 ? const_cast<void*>(H) : w[(k - 1) & 1];
+      a.ld_aux = k == 2 ? ld_h : ld_w;
+      a.omega = (float)omega;
+    }
+    ktimer_begin(s);
+    const int rc = dev_err(appnp::launch_step(APPNP_F32, epi, V, a, s));
+    ktimer_mark(s, APPNP_KT_STEP);
+    if (rc) return rc;
+    src = dst;
+    ld_src = ld_dst;
+  }
+  return APPNP_OK;
+}
+
+// Argument checks of appnp_solve / appnp_solve_bwd, before any device call.  *run = 0: valid and
+// nothing to do (an empty graph or F = 0).
+int check_solve(const appnp_graph* g, const void* in, int64_t ld_in, const void* out,
+                int64_t ld_out, int64_t f, int dtype, int iters, float alpha, bool transposed,
+                int* run) {
+  *run = 0;
+  if (!g) return APPNP_EINVAL;
+  if (f < 0 || f > INT32_MAX || iters < 1 || iters > kSolveMaxIters || !valid_dtype(dtype))
+    return APPNP_EINVAL;
+  if (!valid_solve_alpha(alpha)) return APPNP_EINVAL;
+  if (g->row_lo != 0 || g->row_hi != g->n) return APPNP_EINVAL;  // needs the whole graph
+  if (dtype != APPNP_F32 || !g->symmetric) return APPNP_ENOTSUP;
+  if (transposed && g->mode != APPNP_NORM_SYM && !g->t_row_ptr) return APPNP_ENOTSUP;
+  if (g->n == 0 || f == 0) return APPNP_OK;
+  if (!in || !out || ld_in < f || ld_out < f || in == out) return APPNP_EINVAL;
+  *run = 1;
+  return APPNP_OK;
+}
+
+}  // namespace
+
+int appnp_solve_iterations(float alpha, float tol, int* iters) {
+  if (!iters || !valid_solve_alpha(alpha) || !(tol > 0.0f && tol < 1.0f)) return APPNP_EINVAL;
+  const double rho = 1.0 - (double)alpha;
+  const double sigma = rho / (1.0 + std::sqrt(1.0 - rho * rho));
+  double p = 1.0;  // sigma^m
+  for (int m = 1; m <= kSolveMaxIters; ++m) {
+    p *= sigma;
+    if (2.0 * p / (1.0 + p * p) <= (double)tol) {
+      *iters = m;
+      return APPNP_OK;
+    }
+  }
+  return APPNP_ERANGE;
+}
+
+int appnp_solve_weights(float alpha, int iters, double* omega) {
+  if (!omega || !valid_solve_alpha(alpha) || iters < 1 || iters > kSolveMaxIters)
+    return APPNP_EINVAL;
+  const double rho = 1.0 - (double)alpha;
+  double w = 1.0;
+  for (int k = 0; k < iters; ++k) omega[k] = w = next_omega(rho, k, w);
+  return APPNP_OK;
+}
+
+int appnp_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
+                int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
+                void* stream) {
+  int run = 0;
+  const int rc = check_solve(g, H, ld_h, Z, ld_z, f, dtype, iters, alpha, false, &run);
+  if (rc || !run) return rc;
+  // whole rows, also on a graph with a source-blocked copy: no split layout, no remainder pass
+  return solve_loop(base_args(g, f, alpha), H, ld_h, Z, ld_z, f, iters, alpha, ws, ws_bytes,
+                    as_stream(stream));
+}
+
+int appnp_solve_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, void* dH, int64_t ld_dh,
+                    int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
+                    void* stream) {
+  int run = 0;
+  const int rc = check_solve(g, dZ, ld_dz, dH, ld_dh, f, dtype, iters, alpha, true, &run);
+  if (rc || !run) return rc;
+  // Pi^T = alpha (I - (1-alpha) A_hat^T)^-1: the same solve on A_hat^T, whose spectrum is A_hat's
+  StepArgs a = base_args(g, f, alpha);
+  if (g->mode != APPNP_NORM_SYM) {
+    a.row_ptr = g->t_row_ptr;
+    a.col = g->t_col;
+    a.val = g->t_val;
+    a.heavy = g->t_heavy;
+    a.n_heavy = g->t_n_heavy;
+    a.hub = g->t_hub;
+    a.n_hub = g->t_n_hub;
+  }
+  return solve_loop(a, dZ, ld_dz, dH, ld_dh, f, iters, alpha, ws, ws_bytes, as_stream(stream));
+}
+
 int appnp_spmm(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t rows,
                int64_t cols, const float* B, int64_t ld_b, float* Cm, int64_t ld_c, int64_t f,
                float p_drop, uint64_t seed, int transposed_key, void* stream) {
@@ -1129,9 +1271,12 @@ struct appnp_plan {
   hipGraphExec_t exec = nullptr;
 };
 
-int appnp_plan_create(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
-                      int64_t f, int dtype, int K, float alpha, float p_drop, uint64_t seed,
-                      void* ws, size_t ws_bytes, appnp_plan** out) {
+extern "C++" {  // a template cannot have C linkage
+namespace {
+
+// Capture what `enqueue(stream)` launches into a new plan.
+template <typename Enqueue>
+int plan_capture(Enqueue enqueue, appnp_plan** out) {
   if (!out) return APPNP_EINVAL;
   *out = nullptr;
   hipStream_t cs = nullptr;
@@ -1143,7 +1288,7 @@ int appnp_plan_create(const appnp_graph* g, const void* H, int64_t ld_h, void* Z
   }
   int rc = dev_err(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
   if (rc == APPNP_OK) {
-    rc = appnp_propagate(g, H, ld_h, Z, ld_z, f, dtype, K, alpha, p_drop, seed, ws, ws_bytes, cs);
+    rc = enqueue(static_cast<void*>(cs));
     const hipError_t e = hipStreamEndCapture(cs, &p->graph);  // always end the capture
     if (rc == APPNP_OK) rc = dev_err(e);
   }
@@ -1155,6 +1300,35 @@ int appnp_plan_create(const appnp_graph* g, const void* H, int64_t ld_h, void* Z
   }
   *out = p;
   return APPNP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int appnp_plan_create(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
+                      int64_t f, int dtype, int K, float alpha, float p_drop, uint64_t seed,
+                      void* ws, size_t ws_bytes, appnp_plan** out) {
+  return plan_capture(
+      [&](void* cs) {
+        return appnp_propagate(g, H, ld_h, Z, ld_z, f, dtype, K, alpha, p_drop, seed, ws,
+                               ws_bytes, cs);
+      },
+      out);
+}
+
+int appnp_plan_create_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z,
+                            int64_t ld_z, int64_t f, int dtype, int iters, float alpha, void* ws,
+                            size_t ws_bytes, appnp_plan** out) {
+  if (!out) return APPNP_EINVAL;
+  *out = nullptr;
+  int run = 0;  // bad arguments fail here, before the capture stream is created
+  const int rc = check_solve(g, H, ld_h, Z, ld_z, f, dtype, iters, alpha, false, &run);
+  if (rc) return rc;
+  return plan_capture(
+      [&](void* cs) {
+        return appnp_solve(g, H, ld_h, Z, ld_z, f, dtype, iters, alpha, ws, ws_bytes, cs);
+      },
+      out);
 }
 
 int appnp_plan_launch(const appnp_plan* p, void* stream) {

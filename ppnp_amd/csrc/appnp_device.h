@@ -20,7 +20,13 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 //   FINISH   out = y + aux(fp32) + alpha * H        (remote-column half of a split step; the
 //                                                    last shard group of a pipelined one)
 //   ACCUM    out(fp32) += y                         (a middle shard group of a pipelined step)
-enum Epi { EPI_FWD = 0, EPI_BWD = 1, EPI_PARTIAL = 2, EPI_FINISH = 3, EPI_ACCUM = 4 };
+//   CHEB     out = omega * (y + alpha * H) + (1 - omega) * aux   (Chebyshev step of appnp_solve;
+//                                                    aux = Z_{k-1} in the storage type, may be
+//                                                    the buffer `out` itself: a lane reads its
+//                                                    fragment of aux, then writes the same one)
+enum Epi {
+  EPI_FWD = 0, EPI_BWD = 1, EPI_PARTIAL = 2, EPI_FINISH = 3, EPI_ACCUM = 4, EPI_CHEB = 5
+};
 
 struct StepArgs {
   const int32_t* row_ptr;  // local rows, row_ptr[0] == 0
@@ -31,7 +37,7 @@ struct StepArgs {
   const void* zin;         // all n rows (global index)
   const void* h;           // held rows (local index)
   void* out;               // held rows (local index)
-  void* aux;               // BWD: dH (storage dtype); FINISH: fp32 partial
+  void* aux;               // BWD: dH (storage dtype); FINISH: fp32 partial; CHEB: Z_{k-1}
   int64_t ld_in, ld_h, ld_out, ld_aux;
   int64_t n_rows;          // rows held
   int64_t nnz;             // entries of those rows (< 0: unknown); picks the row shape
@@ -58,6 +64,7 @@ struct StepArgs {
                            // gathered rows of Zin from the Infinity Cache
   float* rem_dh;           // remainder pass, adjoint: dH's remainder columns (rows x ld_rem_dh)
   int64_t ld_rem_dh;
+  float omega;             // CHEB: the step's Chebyshev weight (appnp_solve_weights)
 };
 
 // End of row i's entries in the step's CSR (StepArgs::row_end)

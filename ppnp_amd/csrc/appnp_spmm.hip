@@ -143,6 +143,12 @@ __device__ __forceinline__ void epilogue(const StepArgs& a, int64_t row, int col
 #pragma unroll
     for (int v = 0; v < V; ++v) y[v] += pv[v];
     frag_store<float, V, TAIL>(static_cast<float*>(a.out) + row * a.ld_out + col0, y, rem);
+  } else if constexpr (EPI == EPI_CHEB) {
+    const float back = 1.0f - a.omega;
+#pragma unroll
+    for (int v = 0; v < V; ++v) y[v] = fmaf(a.omega, fmaf(a.alpha, hv[v], y[v]), back * pv[v]);
+    frag_store<T, V, TAIL>(static_cast<T*>(a.out) + row * a.ld_out + col0, y, rem,
+                           a.nt & 4);
   } else {  // EPI_FINISH
 #pragma unroll
     for (int v = 0; v < V; ++v) y[v] = fmaf(a.alpha, hv[v], y[v] + pv[v]);
@@ -151,19 +157,20 @@ __device__ __forceinline__ void epilogue(const StepArgs& a, int64_t row, int col
 }
 
 // The row's epilogue operands, loaded when the row starts so their latency hides under the
-// gathers: H (forward, finish), dH (adjoint, in `aux`) and the fp32 partial of the
-// row-partition steps (accumulate: the partial in `out`; finish: the one in `aux`).
+// gathers: H (forward, finish, Chebyshev), dH (adjoint, in `aux`), Z_{k-1} (Chebyshev, in
+// `aux`) and the fp32 partial of the row-partition steps (accumulate: the partial in `out`;
+// finish: the one in `aux`).
 template <typename T, int V, int EPI, bool TAIL>
 __device__ __forceinline__ void load_h(const StepArgs& a, int64_t row, int col0, float (&hv)[V],
                                        float (&pv)[V], int rem) {
-  if constexpr (EPI == EPI_FWD || EPI == EPI_FINISH) {
+  if constexpr (EPI == EPI_FWD || EPI == EPI_FINISH || EPI == EPI_CHEB) {
     frag_load<T, V, TAIL>(static_cast<const T*>(a.h) + row * a.ld_h + col0, hv, rem,
                           row + 1 < a.n_rows, a.nt & 2);
   } else {
 #pragma unroll
     for (int v = 0; v < V; ++v) hv[v] = 0.0f;
   }
-  if constexpr (EPI == EPI_BWD) {
+  if constexpr (EPI == EPI_BWD || EPI == EPI_CHEB) {
     frag_load<T, V, TAIL>(static_cast<const T*>(a.aux) + row * a.ld_aux + col0, pv, rem,
                           row + 1 < a.n_rows);
   } else if constexpr (EPI == EPI_ACCUM) {
@@ -533,6 +540,7 @@ hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a_in, hipStrea
       case EPI_PARTIAL: return launch_v<float, EPI_PARTIAL>(V, G, wide, uw, un, grid, a, s);
       case EPI_FINISH: return launch_v<float, EPI_FINISH>(V, G, wide, uw, un, grid, a, s);
       case EPI_ACCUM: return launch_v<float, EPI_ACCUM>(V, G, wide, uw, un, grid, a, s);
+      case EPI_CHEB: return launch_v<float, EPI_CHEB>(V, G, wide, uw, un, grid, a, s);
     }
   } else {
     switch (epi) {

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .graph import Graph
-from .ops import propagate
+from .ops import propagate, solve
 from .sparse import SparseFeatures, sparse_linear
 
 
@@ -109,11 +109,19 @@ class APPNP(nn.Module):
     forward(X)           -> raises Exception() (model.py:66-67)
 
     ``edge_drop`` > 0 applies edge dropout inside the propagation kernel in training mode.
+
+    ``exact=True`` is the reference's own model: the propagation is Pi H itself, to the
+    relative tolerance ``tol``, by the Chebyshev solver (ops.solve; fp32, undirected graphs),
+    and ``K`` is ignored.  It takes no edge dropout: a mask that changes per step has no fixed
+    point.
     """
 
     def __init__(self, n_features, n_classes, adj, alpha=0.1, K=10, hidden_dim=64,
-                 drop_prob=0.5, bias=False, mode="sym", edge_drop=0.0, dtype=torch.float32):
+                 drop_prob=0.5, bias=False, mode="sym", edge_drop=0.0, dtype=torch.float32,
+                 exact=False, tol=1e-6):
         super().__init__()
+        if exact and edge_drop > 0:
+            raise ValueError("exact=True takes no edge dropout (edge_drop must be 0)")
         import scipy.sparse as sp
 
         self.encoder = _encoder(n_features, n_classes, hidden_dim, drop_prob, bias)
@@ -132,6 +140,8 @@ class APPNP(nn.Module):
         self.mode = mode
         self.edge_drop = float(edge_drop)
         self.prop_dtype = dtype
+        self.exact = bool(exact)
+        self.tol = float(tol)
         self.ppr_topk = None  # batch-main.py:113-117 sparsification of the lazy ``ppr``
         self._graph = None
         self._ppr = None  # (device, topk, dense Pi) built on first access of ``ppr``
@@ -175,6 +185,8 @@ class APPNP(nn.Module):
         return sum((torch.sum(param ** 2) for param in self._reg_params))
 
     def propagate(self, H):
+        if self.exact:
+            return solve(self.graph(), H.to(self.prop_dtype), self.alpha, self.tol).to(H.dtype)
         p = self.edge_drop if self.training else 0.0
         seed = int(torch.randint(0, 2**62, (1,)).item()) if p > 0 else 0
         Hc = H.to(self.prop_dtype)
@@ -195,7 +207,7 @@ class APPNP(nn.Module):
         xs = (X.indptr, X.indices, X.data) if isinstance(X, SparseFeatures) else (X,)
         state = (*xs, *self.parameters(), *self.buffers())
         return (state, tuple(t._version for t in state), self.K, self.alpha, self.mode,
-                self.prop_dtype)
+                self.prop_dtype, self.exact, self.tol)
 
     @staticmethod
     def _memo_match(a, b) -> bool:

@@ -138,6 +138,100 @@ def propagate(graph: Graph, H: torch.Tensor, K: int = 10, alpha: float = 0.1,
                                         s - 2**64 if s >= 2**63 else s)
 
 
+# ---- exact PPNP: the Chebyshev solver (appnp_solve) ---------------------------------------
+
+
+def solve_iterations(alpha: float = 0.1, tol: float = 1e-6) -> int:
+    """Steps the solver takes for ``tol`` (``appnp_solve_iterations``): the smallest m with
+    2 sigma^m / (1 + sigma^2m) <= tol, sigma = rho / (1 + sqrt(1 - rho^2)), rho = 1 - alpha
+    (alpha = 0.1: 27 / 32 / 36 for 1e-5 / 1e-6 / 1e-7).  Host only."""
+    m = C.c_int()
+    _lib.check("appnp_solve_iterations",
+               _lib.load().appnp_solve_iterations(float(alpha), float(tol), C.byref(m)))
+    return m.value
+
+
+def solve_weights(alpha: float, iters: int) -> list[float]:
+    """The Chebyshev weights w_1 .. w_iters in fp64 (``appnp_solve_weights``).  Host only."""
+    w = (C.c_double * max(int(iters), 1))()
+    _lib.check("appnp_solve_weights", _lib.load().appnp_solve_weights(float(alpha), int(iters), w))
+    return list(w)
+
+
+def _solve_call(name: str, graph: Graph, X: torch.Tensor, iters: int, alpha: float,
+                out: torch.Tensor | None) -> torch.Tensor:
+    _check_dense(name, X, graph, graph.n)
+    Y = torch.empty_like(X, memory_format=torch.contiguous_format) if out is None else out
+    _check_dense("out", Y, graph, graph.n)
+    if Y.dtype != X.dtype or Y.shape != X.shape:
+        raise ValueError(f"out must match {name} in shape and dtype")
+    lib = _lib.load()
+    fn_name = "appnp_solve" if name == "H" else "appnp_solve_bwd"
+    dt = _DTYPES[X.dtype]
+    f = int(X.shape[1])
+    ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(Y), dt)) if iters >= 2 else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    with torch.cuda.device(graph.device):
+        rc = getattr(lib, fn_name)(graph.handle, _vp(X), _ld(X), _vp(Y), _ld(Y), f, dt,
+                                   int(iters), float(alpha), _vp(ws), ws_bytes,
+                                   _stream(graph.device))
+    _lib.check(fn_name, rc)
+    return Y
+
+
+def solve_forward(graph: Graph, H: torch.Tensor, iters: int, alpha: float,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Z = Pi H after ``iters`` Chebyshev steps via ``appnp_solve`` (one fused HIP launch per
+    step).  fp32, undirected graphs, whole rows; see include/ppnp_amd.h."""
+    return _solve_call("H", graph, H, iters, alpha, out)
+
+
+def solve_backward(graph: Graph, dZ: torch.Tensor, iters: int, alpha: float) -> torch.Tensor:
+    """dH = Pi^T dZ via ``appnp_solve_bwd``: the same solve on A_hat^T, i.e. the gradient of the
+    converged operator (rw needs ``Graph(..., transpose=True)``)."""
+    return _solve_call("dZ", graph, dZ.contiguous(), iters, alpha, None)
+
+
+@torch.library.custom_op("ppnp_amd::solve", mutates_args=(), device_types="cuda")
+def _solve_op(H: torch.Tensor, graph_key: int, iters: int, alpha: float) -> torch.Tensor:
+    return solve_forward(Graph.lookup(graph_key), H.contiguous(), iters, alpha)
+
+
+@_solve_op.register_fake
+def _(H, graph_key, iters, alpha):
+    return torch.empty(H.shape, dtype=H.dtype, device=H.device)
+
+
+@torch.library.custom_op("ppnp_amd::solve_bwd", mutates_args=(), device_types="cuda")
+def _solve_bwd_op(dZ: torch.Tensor, graph_key: int, iters: int, alpha: float) -> torch.Tensor:
+    return solve_backward(Graph.lookup(graph_key), dZ, iters, alpha)
+
+
+@_solve_bwd_op.register_fake
+def _(dZ, graph_key, iters, alpha):
+    return torch.empty(dZ.shape, dtype=dZ.dtype, device=dZ.device)
+
+
+def _solve_setup(ctx, inputs, output):
+    ctx.args = inputs[1:]
+
+
+def _solve_grad(ctx, dZ):
+    return (torch.ops.ppnp_amd.solve_bwd(dZ, *ctx.args), None, None, None)
+
+
+_solve_op.register_autograd(_solve_grad, setup_context=_solve_setup)
+
+
+def solve(graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
+          iters: int | None = None) -> torch.Tensor:
+    """Differentiable exact PPNP propagation Pi H, Pi = alpha (I - (1-alpha) A_hat)^-1, to the
+    relative tolerance ``tol`` (the ``ppnp_amd::solve`` op): ``solve_iterations(alpha, tol)``
+    Chebyshev steps unless ``iters`` is given.  fp32 H on an undirected graph."""
+    m = solve_iterations(alpha, tol) if iters is None else int(iters)
+    return torch.ops.ppnp_amd.solve(H, graph.key, m, float(alpha))
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:
@@ -268,6 +362,31 @@ class PropagatePlan:
             self.close()
         except Exception:
             pass
+
+
+class SolvePlan(PropagatePlan):
+    """A captured exact solve (``appnp_plan_create_solve``): the Chebyshev steps of
+    ``solve_forward`` recorded once into a hipGraph for fixed H / Z buffers.  Used like
+    ``PropagatePlan``: refill ``plan.H`` in place, call ``plan()``, read ``plan.Z``."""
+
+    def __init__(self, graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
+                 iters: int | None = None):
+        _check_dense("H", H, graph, graph.n)
+        self.graph, self.H = graph, H
+        self.iters = solve_iterations(alpha, tol) if iters is None else int(iters)
+        self.Z = torch.empty_like(H, memory_format=torch.contiguous_format)
+        lib = _lib.load()
+        dt = _DTYPES[H.dtype]
+        f = int(H.shape[1])
+        self._ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(self.Z), dt))
+        self._ws = torch.empty(max(self._ws_bytes, 1), dtype=torch.uint8, device=graph.device)
+        self._p = C.c_void_p()
+        torch.cuda.current_stream(graph.device).synchronize()  # buffers allocated before capture
+        with torch.cuda.device(graph.device):
+            rc = lib.appnp_plan_create_solve(graph.handle, _vp(H), _ld(H), _vp(self.Z),
+                                             _ld(self.Z), f, dt, self.iters, float(alpha),
+                                             _vp(self._ws), self._ws_bytes, C.byref(self._p))
+        _lib.check("appnp_plan_create_solve", rc)
 
 
 KERNEL_KINDS = {_lib.KT_COPY: "copy", _lib.KT_STEP: "step", _lib.KT_REM: "rem",

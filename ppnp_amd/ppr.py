@@ -24,7 +24,7 @@ from __future__ import annotations
 import torch
 
 from .graph import Graph
-from .ops import propagate_forward
+from .ops import propagate_forward, solve_forward, solve_iterations
 
 
 def _degrees(graph: Graph):
@@ -33,22 +33,27 @@ def _degrees(graph: Graph):
     return 1.0 / dinv
 
 
-def ppr_columns(graph: Graph, idx: torch.Tensor, K: int = 10, alpha: float = 0.1):
-    """Pi[:, idx] (N x B, fp32) = APPNP_K of the one-hot columns of idx."""
+def ppr_columns(graph: Graph, idx: torch.Tensor, K: int = 10, alpha: float = 0.1,
+                tol: float | None = None):
+    """Pi[:, idx] (N x B, fp32) = APPNP_K of the one-hot columns of idx; with ``tol`` the exact
+    columns to that relative tolerance by the Chebyshev solver (ops.solve_forward), K ignored."""
     idx = torch.as_tensor(idx, device=graph.device).long()
     B = int(idx.numel())
     E = torch.zeros(graph.n, B, dtype=torch.float32, device=graph.device)
     E[idx, torch.arange(B, device=graph.device)] = 1.0
+    if tol is not None:
+        return solve_forward(graph, E, solve_iterations(alpha, tol), alpha)
     return propagate_forward(graph, E, K, alpha)
 
 
-def ppr_rows(graph: Graph, idx, K: int = 10, alpha: float = 0.1, topk: int | None = None):
+def ppr_rows(graph: Graph, idx, K: int = 10, alpha: float = 0.1, topk: int | None = None,
+             tol: float | None = None):
     """Pi[idx, :] as a dense B x N fp32 tensor (entries outside each row's top-k zeroed when
-    ``topk`` is given)."""
+    ``topk`` is given).  ``tol``: as for ``ppr_columns``."""
     if not graph.symmetric:
         raise ValueError("ppr_rows needs an undirected graph (symmetric A)")
     idx = torch.as_tensor(idx, device=graph.device).long()
-    cols = ppr_columns(graph, idx, K, alpha)  # N x B
+    cols = ppr_columns(graph, idx, K, alpha, tol)  # N x B
     if graph.mode == "sym":
         rows = cols.t().contiguous()
     else:  # rw: Pi[i, :] = D * Pi[:, i] / d_i
@@ -61,16 +66,18 @@ def ppr_rows(graph: Graph, idx, K: int = 10, alpha: float = 0.1, topk: int | Non
     return rows
 
 
-def dense_ppr(graph: Graph, K: int = 10, alpha: float = 0.1, chunk: int = 1024) -> torch.Tensor:
+def dense_ppr(graph: Graph, K: int = 10, alpha: float = 0.1, chunk: int = 1024,
+              tol: float | None = None) -> torch.Tensor:
     """All of Pi (N x N fp32), row chunks of ``ppr_rows``: the truncated series of
-    compute_ppr (helpers.py:68-71).  Small graphs only (materialises N x N)."""
+    compute_ppr (helpers.py:68-71), or with ``tol`` the solver's rows.  Small graphs only
+    (materialises N x N)."""
     n = graph.n
     if n * n > 2**31:
         raise ValueError("dense_ppr materialises N x N: N too large")
     P = torch.empty(n, n, dtype=torch.float32, device=graph.device)
     for s in range(0, n, chunk):
         idx = torch.arange(s, min(n, s + chunk), device=graph.device)
-        P[s:s + len(idx)] = ppr_rows(graph, idx, K, alpha)
+        P[s:s + len(idx)] = ppr_rows(graph, idx, K, alpha, tol=tol)
     return P
 
 

@@ -172,7 +172,9 @@ def run_once(adj, attr, labels, args, device):
         model = PPNP(n_features=X.shape[1], n_classes=n_classes, ppr=ppr).to(device)
     else:
         model = APPNP(n_features=X.shape[1], n_classes=n_classes, adj=adj, alpha=args.alpha,
-                      K=args.K, edge_drop=args.edge_drop).to(device)
+                      K=args.K, edge_drop=args.edge_drop,
+                      exact=getattr(args, "exact", False),
+                      tol=getattr(args, "tol", 1e-6)).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     early_stopping = SimpleEarlyStopping(model)
     t = time.time()
@@ -231,6 +233,10 @@ def parse_args(argv=None):
     p.add_argument("--alpha", type=float, default=0.1)
     p.add_argument("--K", type=int, default=10)
     p.add_argument("--edge-drop", type=float, default=0.0)
+    p.add_argument("--exact", action="store_true",
+                   help="--model appnp: propagate with the exact PPNP solver (K is ignored)")
+    p.add_argument("--tol", type=float, default=1e-6,
+                   help="relative tolerance of --exact")
     p.add_argument("--model", default="appnp", choices=["appnp", "ppnp"])
     p.add_argument("--sparse-x", action="store_true",
                    help="keep the attribute matrix as a CSR on the GPU (sparse encoder input)")
