@@ -110,6 +110,21 @@ inline int dev_err(hipError_t e) {
   return APPNP_EDEVICE;
 }
 
+// One launch (or copy) on `s` between the kernel timer's two events, tagged `kind` (APPNP_KT_*).
+// Every launch of this unit's propagation entry points goes through here.
+template <typename Launch>
+inline int timed(hipStream_t s, int kind, Launch launch) {
+  ktimer_begin(s);
+  const int rc = dev_err(launch());
+  ktimer_mark(s, kind);
+  return rc;
+}
+
+inline int timed_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s,
+                      int kind = APPNP_KT_STEP) {
+  return timed(s, kind, [&] { return appnp::launch_step(dtype, epi, V, a, s); });
+}
+
 inline int64_t elem_size(int dtype) { return dtype == APPNP_F32 ? 4 : 2; }
 
 inline bool valid_dtype(int dtype) { return dtype == APPNP_F32 || dtype == APPNP_BF16; }
@@ -162,13 +177,49 @@ StepArgs base_args(const appnp_graph* g, int64_t f, float alpha) {
   return a;
 }
 
-constexpr double kSplitMaxNear = 0.5;
+// A_hat^T for the adjoints of a graph whose A_hat is not symmetric: the transposed CSR built at
+// creation (APPNP_GRAPH_TRANSPOSE) and its heavy / hub rows
+void use_transpose(StepArgs& a, const appnp_graph* g) {
+  a.row_ptr = g->t_row_ptr;
+  a.col = g->t_col;
+  a.val = g->t_val;
+  a.heavy = g->t_heavy;
+  a.n_heavy = g->t_n_heavy;
+  a.hub = g->t_hub;
+  a.n_hub = g->t_n_hub;
+}
 
-// the timer kind of an appnp_step / appnp_step_split launch on `part`
-inline int part_kind(int part) {
-  return part == APPNP_PART_LOCAL ? APPNP_KT_LOCAL
-                                  : part == APPNP_PART_REMOTE ? APPNP_KT_REMOTE : APPNP_KT_STEP;
-}  // split rows only below this gather locality
+// The heavy / hub lists describe the whole held rows: a step over part of their entries (the
+// LOCAL / REMOTE half, a shard range) runs without them.
+void drop_row_lists(StepArgs& a) {
+  a.heavy = nullptr;
+  a.n_heavy = 0;
+  a.hub = nullptr;
+  a.n_hub = 0;
+}
+
+// The caller's workspace from its 256-B aligned base on: the ping-pong buffers carved from it
+// (null beyond `count`) and the bytes it holds from that base, buffers included.
+struct Workspace {
+  void* buf[2] = {nullptr, nullptr};
+  size_t room = 0;
+};
+
+// Carve `count` (0..2) buffers of `bytes` each; APPNP_EINVAL when they are needed and `ws` is
+// null or too small.  count = 0 touches nothing: a caller that needs no buffer may pass none.
+int carve(void* ws, size_t ws_bytes, int count, int64_t bytes, Workspace* w) {
+  *w = Workspace{};
+  if (count <= 0) return APPNP_OK;
+  if (!ws) return APPNP_EINVAL;
+  const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
+  const uintptr_t aligned = (base + 255) & ~uintptr_t(255);
+  if (ws_bytes < (size_t)(count * bytes) + (aligned - base)) return APPNP_EINVAL;
+  w->room = ws_bytes - (aligned - base);
+  for (int i = 0; i < count; ++i) w->buf[i] = reinterpret_cast<char*>(aligned) + i * bytes;
+  return APPNP_OK;
+}
+
+constexpr double kSplitMaxNear = 0.5;  // split rows only below this gather locality
 
 // Whether every operand allows 16-B vectors: leading dimensions multiples of 4 floats and
 // 16-B aligned base pointers (null pointers ignored).  The split path reads and writes H / Z
@@ -218,11 +269,31 @@ int64_t split_point(const appnp_graph* g, int64_t f, int dtype, bool aligned) {
   return r ? f - r : 0;
 }
 
-// Bytes of the two split buffers ([n, fs] + [n, 4 rb_lpe] fp32 each, 256-B aligned)
-inline void split_sizes(const appnp_graph* g, int64_t n, int64_t fs, int64_t* main_b,
-                        int64_t* buf_b) {
-  *main_b = (n * fs * 4 + 255) / 256 * 256;
-  *buf_b = (*main_b + n * 16 * g->rb_lpe + 255) / 256 * 256;
+// The two split buffers of [n, f] fp32 rows with main part fs, back to back from a 256-B aligned
+// base: each a main part [n, fs] and, 256-B aligned behind it, a remainder part [n, 4 rb_lpe]
+// (fs = 0: narrow rows, all in the remainder pass).
+struct SplitBufs {
+  char* base;
+  int64_t main_b, buf_b;  // bytes of a main part; of a whole buffer
+  SplitBufs(const appnp_graph* g, int64_t n, int64_t fs, void* base_)
+      : base(static_cast<char*>(base_)),
+        main_b((n * fs * 4 + 255) / 256 * 256),
+        buf_b((main_b + n * 16 * g->rb_lpe + 255) / 256 * 256) {}
+  int64_t bytes() const { return 2 * buf_b; }
+  float* main(int i) const { return reinterpret_cast<float*>(base + i * buf_b); }
+  float* rem(int i) const { return reinterpret_cast<float*>(base + i * buf_b + main_b); }
+};
+
+// What both split loops begin with: `src` (H, or dZ) copied into split buffer 0, and the K
+// remainder passes to come counted on the graph.
+int split_copy_in(const appnp_graph* g, const void* src, int64_t ld, int64_t n, int64_t f,
+                  int64_t fs, int K, const SplitBufs& b, hipStream_t s) {
+  const int rc = timed(s, APPNP_KT_COPY, [&] {
+    return appnp::launch_split_copy(static_cast<const float*>(src), ld, n, f, fs, 4 * g->rb_lpe,
+                                    b.main(0), b.rem(0), appnp::remainder_scale(g), s);
+  });
+  g->rem_launches.fetch_add(K, std::memory_order_relaxed);
+  return rc;
 }
 
 // The forward loop in the split layout (appnp_blocks.hip).  Propagation is column-separable,
@@ -238,19 +309,12 @@ inline void split_sizes(const appnp_graph* g, int64_t n, int64_t fs, int64_t* ma
 // the total measured within 1 % of running them one after the other.
 int propagate_split(const appnp_graph* g, const StepArgs& a0, const void* H, int64_t ld_h,
                     void* Z, int64_t ld_z, int64_t fs, int K, float p_drop, uint64_t seed,
-                    char* ws, int64_t main_b, int64_t buf_b, hipStream_t s) {
-  const int64_t n = a0.n_rows, f = a0.f;
+                    const SplitBufs& b, hipStream_t s) {
+  const int64_t f = a0.f;
   const int lpe = g->rb_lpe, rw = 4 * lpe;  // floats per remainder row
-  char* bufs[2] = {ws, ws + buf_b};
-  auto main_of = [&](int i) { return reinterpret_cast<float*>(bufs[i]); };
-  auto rem_of = [&](int i) { return reinterpret_cast<float*>(bufs[i] + main_b); };
   const float* h = static_cast<const float*>(H);
   float* z = static_cast<float*>(Z);
-  ktimer_begin(s);
-  int rc = dev_err(appnp::launch_split_copy(h, ld_h, n, f, fs, rw, main_of(0), rem_of(0),
-                                            appnp::remainder_scale(g), s));
-  ktimer_mark(s, APPNP_KT_COPY);
-  g->rem_launches.fetch_add(K, std::memory_order_relaxed);
+  int rc = split_copy_in(g, H, ld_h, a0.n_rows, f, fs, K, b, s);
   StepArgs am = a0, ar = a0;  // main / remainder chain
   am.f = (int32_t)fs;
   am.h = H;
@@ -261,24 +325,19 @@ int propagate_split(const appnp_graph* g, const StepArgs& a0, const void* H, int
     const int dst = cur ^ 1;
     const bool last = k == K - 1;
     set_drop(am, p_drop, seed, k);
-    am.zin = main_of(cur);
-    am.out = last ? Z : main_of(dst);
+    am.zin = b.main(cur);
+    am.out = last ? Z : b.main(dst);
     am.ld_out = last ? ld_z : fs;
-    if (fs > 0) {
-      ktimer_begin(s);
-      rc = dev_err(appnp::launch_step(APPNP_F32, appnp::EPI_FWD, 4, am, s));
-      ktimer_mark(s, APPNP_KT_STEP);
-    }
+    if (fs > 0) rc = timed_step(APPNP_F32, appnp::EPI_FWD, 4, am, s);
     if (rc) break;
     set_drop(ar, p_drop, seed, k);
     // LPE = 1: nv = 4 into the next remainder buffer (the shipped form); LPE > 1: nv is always
     // the valid remainder columns, to_rem says where the row goes
     const int nv = (lpe == 1 && !last) ? 4 : (int)(f - fs);
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_remainder(g, ar, appnp::EPI_FWD, rem_of(cur), h + fs, ld_h,
-                                         last ? z + fs : rem_of(dst), last ? ld_z : rw, nv,
-                                         !last, s));
-    ktimer_mark(s, APPNP_KT_REM);
+    rc = timed(s, APPNP_KT_REM, [&] {
+      return appnp::launch_remainder(g, ar, appnp::EPI_FWD, b.rem(cur), h + fs, ld_h,
+                                     last ? z + fs : b.rem(dst), last ? ld_z : rw, nv, !last, s);
+    });
     cur = dst;
   }
   return rc;
@@ -289,19 +348,10 @@ int propagate_split(const appnp_graph* g, const StepArgs& a0, const void* H, int
 // self-adjoint A_hat.  dH = alpha dZ is set by the caller.
 int propagate_bwd_split(const appnp_graph* g, const StepArgs& a0, const void* dZ, int64_t ld_dz,
                         void* dH, int64_t ld_dh, int64_t fs, int K, float alpha, float p_drop,
-                        uint64_t seed, char* ws, int64_t main_b, int64_t buf_b,
-                        hipStream_t s) {
-  const int64_t n = a0.n_rows, f = a0.f;
-  const int lpe = g->rb_lpe, rw = 4 * lpe;
-  char* bufs[2] = {ws, ws + buf_b};
-  auto main_of = [&](int i) { return reinterpret_cast<float*>(bufs[i]); };
-  auto rem_of = [&](int i) { return reinterpret_cast<float*>(bufs[i] + main_b); };
-  ktimer_begin(s);
-  int rc = dev_err(appnp::launch_split_copy(static_cast<const float*>(dZ), ld_dz, n, f, fs, rw,
-                                            main_of(0), rem_of(0), appnp::remainder_scale(g),
-                                            s));
-  ktimer_mark(s, APPNP_KT_COPY);
-  g->rem_launches.fetch_add(K, std::memory_order_relaxed);
+                        uint64_t seed, const SplitBufs& b, hipStream_t s) {
+  const int64_t f = a0.f;
+  const int rw = 4 * g->rb_lpe;
+  int rc = split_copy_in(g, dZ, ld_dz, a0.n_rows, f, fs, K, b, s);
   StepArgs am = a0, ar = a0;  // main / remainder chain
   am.f = (int32_t)fs;
   am.aux = dH;
@@ -315,21 +365,16 @@ int propagate_bwd_split(const appnp_graph* g, const StepArgs& a0, const void* dZ
     const float a_k = k >= 1 ? alpha : 1.0f;
     set_drop(am, p_drop, seed, k);
     am.alpha = a_k;
-    am.zin = main_of(cur);
-    am.out = k == 0 ? nullptr : main_of(dst);
-    if (fs > 0) {
-      ktimer_begin(s);
-      rc = dev_err(appnp::launch_step(APPNP_F32, appnp::EPI_BWD, 4, am, s));
-      ktimer_mark(s, APPNP_KT_STEP);
-    }
+    am.zin = b.main(cur);
+    am.out = k == 0 ? nullptr : b.main(dst);
+    if (fs > 0) rc = timed_step(APPNP_F32, appnp::EPI_BWD, 4, am, s);
     if (rc) break;
     set_drop(ar, p_drop, seed, k);
     ar.alpha = a_k;
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_remainder(g, ar, appnp::EPI_BWD, rem_of(cur), dh_rem, ld_dh,
-                                         k == 0 ? nullptr : rem_of(dst), rw, (int)(f - fs),
-                                         true, s));
-    ktimer_mark(s, APPNP_KT_REM);
+    rc = timed(s, APPNP_KT_REM, [&] {
+      return appnp::launch_remainder(g, ar, appnp::EPI_BWD, b.rem(cur), dh_rem, ld_dh,
+                                     k == 0 ? nullptr : b.rem(dst), rw, (int)(f - fs), true, s);
+    });
     cur = dst;
   }
   return rc;
@@ -479,11 +524,7 @@ size_t appnp_workspace_bytes(const appnp_graph* g, int64_t f, int64_t ld, int dt
   // the split layout: two buffers [n, fs] + [n, 4 rb_lpe] (a W8 / W16 remainder row is wider
   // than the packed row's tail), plus the alignment of the base
   const int64_t r = (g->row_lo == 0 && g->row_hi == g->n) ? remainder_cols(g, f, dtype, true) : 0;
-  if (r > 0) {
-    int64_t main_b = 0, buf_b = 0;
-    split_sizes(g, rows, f - r, &main_b, &buf_b);
-    need = std::max<int64_t>(need, 2 * buf_b + 256);
-  }
+  if (r > 0) need = std::max<int64_t>(need, SplitBufs(g, rows, f - r, nullptr).bytes() + 256);
   return (size_t)need;
 }
 
@@ -532,24 +573,17 @@ int appnp_propagate(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, 
   if (!H || !Z || ld_h < f || ld_z < f || H == Z) return APPNP_EINVAL;
   const hipStream_t s = as_stream(stream);
   const int64_t es = elem_size(dtype);
-  if (K == 0) {
-    ktimer_begin(s);
-    rc = dev_err(hipMemcpy2DAsync(Z, ld_z * es, H, ld_h * es, f * es, n,
-                                  hipMemcpyDeviceToDevice, s));
-    ktimer_mark(s, APPNP_KT_COPY);
-    return rc;
-  }
+  if (K == 0)
+    return timed(s, APPNP_KT_COPY, [&] {
+      return hipMemcpy2DAsync(Z, ld_z * es, H, ld_h * es, f * es, n, hipMemcpyDeviceToDevice, s);
+    });
+  // Z and one workspace buffer alternate (K = 1 needs none)
   const int64_t ld_w = line_ld(f, dtype);
-  void* const ws_orig = ws;
-  if (K >= 2) {
-    if (!ws) return APPNP_EINVAL;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
-    const uintptr_t aligned = (base + 255) & ~uintptr_t(255);
-    if (ws_bytes < (size_t)(n * ld_w * es) + (aligned - base)) return APPNP_EINVAL;
-    ws = reinterpret_cast<void*>(aligned);
-  }
+  Workspace w;
+  rc = carve(ws, ws_bytes, std::min(K - 1, 1), n * ld_w * es, &w);
+  if (rc) return rc;
   const int64_t lds[3] = {ld_h, ld_z, ld_w};
-  const void* ptrs[3] = {H, Z, K >= 2 ? ws : nullptr};
+  const void* ptrs[3] = {H, Z, w.buf[0]};
   const int V = appnp::pick_vec(dtype, f, lds, 3, ptrs, 3);
 
   StepArgs a = base_args(g, f, alpha);
@@ -559,32 +593,24 @@ int appnp_propagate(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, 
   const void* hz[2] = {H, Z};
   const int64_t r = K >= 2 ? remainder_cols(g, f, dtype, vec16(hz_lds, 2, hz, 2)) : 0;
   if (r > 0) {
-    // two split buffers [n, fs] + [n, 4 rb_lpe] fp32 in the workspace, each 256-B aligned
-    // (fs = 0: narrow rows, all in the remainder pass)
-    const int64_t fs = f - r;
-    int64_t main_b = 0, buf_b = 0;
-    split_sizes(g, n, fs, &main_b, &buf_b);
-    const size_t used = (size_t)(reinterpret_cast<uintptr_t>(ws) -
-                                 reinterpret_cast<uintptr_t>(ws_orig));
-    if (ws_bytes >= used + 2 * (size_t)buf_b)
-      return propagate_split(g, a, H, ld_h, Z, ld_z, fs, K, p_drop, seed,
-                             static_cast<char*>(ws), main_b, buf_b, s);
+    // the split buffers take the place of the ping-pong buffer, where the workspace holds them
+    const SplitBufs b(g, n, f - r, w.buf[0]);
+    if (w.room >= (size_t)b.bytes())
+      return propagate_split(g, a, H, ld_h, Z, ld_z, f - r, K, p_drop, seed, b, s);
   }
   const void* src = H;
   int64_t ld_src = ld_h;
   for (int k = 0; k < K; ++k) {
     // the last iteration must land in Z: alternate backwards from it
     const bool to_z = ((K - 1 - k) % 2) == 0;
-    void* dst = to_z ? Z : ws;
+    void* dst = to_z ? Z : w.buf[0];
     const int64_t ld_dst = to_z ? ld_z : ld_w;
     a.zin = src;
     a.ld_in = ld_src;
     a.out = dst;
     a.ld_out = ld_dst;
     set_drop(a, p_drop, seed, k);
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_step(dtype, appnp::EPI_FWD, V, a, s));
-    ktimer_mark(s, APPNP_KT_STEP);
+    rc = timed_step(dtype, appnp::EPI_FWD, V, a, s);
     if (rc) return rc;
     src = dst;
     ld_src = ld_dst;
@@ -607,80 +633,54 @@ int appnp_propagate_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, voi
   if (!dZ || !dH || ld_dz < f || ld_dh < f || dZ == dH) return APPNP_EINVAL;
   const hipStream_t s = as_stream(stream);
   const int64_t es = elem_size(dtype);
-  if (K == 0) {
-    ktimer_begin(s);
-    rc = dev_err(hipMemcpy2DAsync(dH, ld_dh * es, dZ, ld_dz * es, f * es, n,
-                                  hipMemcpyDeviceToDevice, s));
-    ktimer_mark(s, APPNP_KT_COPY);
-    return rc;
-  }
+  if (K == 0)
+    return timed(s, APPNP_KT_COPY, [&] {
+      return hipMemcpy2DAsync(dH, ld_dh * es, dZ, ld_dz * es, f * es, n, hipMemcpyDeviceToDevice,
+                              s);
+    });
+  // G_{K-1} .. G_1 alternate between two workspace buffers (K = 2 needs one, K = 1 none)
   const int64_t ld_w = line_ld(f, dtype);
-  const int64_t buf = n * ld_w * es;
-  const int nbuf = K >= 3 ? 2 : (K == 2 ? 1 : 0);
-  void* const ws_orig = ws;
-  if (nbuf > 0) {
-    if (!ws) return APPNP_EINVAL;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
-    const uintptr_t aligned = (base + 255) & ~uintptr_t(255);
-    if (ws_bytes < (size_t)(nbuf * buf) + (aligned - base)) return APPNP_EINVAL;
-    ws = reinterpret_cast<void*>(aligned);
-  }
-  void* w0 = ws;
-  void* w1 = nbuf == 2 ? static_cast<char*>(ws) + buf : nullptr;
+  Workspace w;
+  rc = carve(ws, ws_bytes, std::min(K - 1, 2), n * ld_w * es, &w);
+  if (rc) return rc;
   const int64_t lds[3] = {ld_dz, ld_dh, ld_w};
-  const void* ptrs[4] = {dZ, dH, w0, w1};
+  // at K = 1 the workspace pointer counts as the caller gave it, though no step touches it
+  const void* ptrs[4] = {dZ, dH, K == 1 ? ws : w.buf[0], w.buf[1]};
   const int V = appnp::pick_vec(dtype, f, lds, 3, ptrs, 4);
 
   // dH = alpha * dZ  (the k = K term), then G_k = (1-alpha) M_k^T G_{k+1},
   // dH += alpha G_k (k >= 1) / dH += G_0.
-  ktimer_begin(s);
-  rc = dev_err(appnp::launch_scale_rows(dtype, dZ, ld_dz, dH, ld_dh, n, f, alpha, s));
-  ktimer_mark(s, APPNP_KT_COPY);
+  rc = timed(s, APPNP_KT_COPY, [&] {
+    return appnp::launch_scale_rows(dtype, dZ, ld_dz, dH, ld_dh, n, f, alpha, s);
+  });
   if (rc) return rc;
   // split rows (self-adjoint A_hat: the source-blocked copy of A_hat is that of A_hat^T)
   const int64_t dd_lds[2] = {ld_dz, ld_dh};
   const void* dd[2] = {dZ, dH};
   const int64_t r =
       (self_adjoint && K >= 2) ? remainder_cols(g, f, dtype, vec16(dd_lds, 2, dd, 2)) : 0;
-  const int64_t fs = f - r;
-  int64_t main_b = 0, buf_b = 0;
-  bool split = r > 0;
-  if (split) {
-    split_sizes(g, n, fs, &main_b, &buf_b);
-    const size_t used = (size_t)(reinterpret_cast<uintptr_t>(ws) -
-                                 reinterpret_cast<uintptr_t>(ws_orig));
-    if (ws_bytes < used + 2 * (size_t)buf_b) split = false;  // too small: whole rows
-  }
   StepArgs a = base_args(g, f, alpha);
-  if (!self_adjoint) {
-    a.row_ptr = g->t_row_ptr;
-    a.col = g->t_col;
-    a.val = g->t_val;
-    a.heavy = g->t_heavy;
-    a.n_heavy = g->t_n_heavy;
-    a.hub = g->t_hub;
-    a.n_hub = g->t_n_hub;
-  }
+  if (!self_adjoint) use_transpose(a, g);
   a.tkey = 1;  // entry (j, i) of A_hat^T carries the mask of forward edge (i, j)
-  if (split)
-    return propagate_bwd_split(g, a, dZ, ld_dz, dH, ld_dh, fs, K, alpha, p_drop, seed,
-                               static_cast<char*>(ws), main_b, buf_b, s);
+  if (r > 0) {
+    const SplitBufs b(g, n, f - r, w.buf[0]);
+    if (w.room >= (size_t)b.bytes())  // else too small: whole rows
+      return propagate_bwd_split(g, a, dZ, ld_dz, dH, ld_dh, f - r, K, alpha, p_drop, seed, b, s);
+  }
   a.aux = dH;
   a.ld_aux = ld_dh;
   const void* src = dZ;
   int64_t ld_src = ld_dz;
   int flip = 0;
   for (int k = K - 1; k >= 0; --k) {
-    void* dst = k == 0 ? nullptr : (flip ? w1 : w0);
+    void* dst = k == 0 ? nullptr : w.buf[flip];
     a.zin = src;
     a.ld_in = ld_src;
     a.out = dst;
     a.ld_out = ld_w;
     a.alpha = k >= 1 ? alpha : 1.0f;
     set_drop(a, p_drop, seed, k);
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_step(dtype, appnp::EPI_BWD, V, a, s));
-    ktimer_mark(s, APPNP_KT_STEP);
+    rc = timed_step(dtype, appnp::EPI_BWD, V, a, s);
     if (rc) return rc;
     src = dst;
     ld_src = ld_w;
@@ -710,16 +710,10 @@ int solve_loop(StepArgs a, const void* H, int64_t ld_h, void* Z, int64_t ld_z, i
                int iters, float alpha, void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t n = a.n_rows;
   const int64_t ld_w = line_ld(f, APPNP_F32);
-  const int64_t buf = n * ld_w * 4;
-  const int nbuf = iters >= 3 ? 2 : (iters == 2 ? 1 : 0);
-  if (nbuf > 0) {
-    if (!ws) return APPNP_EINVAL;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(ws);
-    const uintptr_t aligned = (base + 255) & ~uintptr_t(255);
-    if (ws_bytes < (size_t)(nbuf * buf) + (aligned - base)) return APPNP_EINVAL;
-    ws = reinterpret_cast<void*>(aligned);
-  }
-  void* w[2] = {nbuf >= 1 ? ws : nullptr, nbuf == 2 ? static_cast<char*>(ws) + buf : nullptr};
+  Workspace carved;  // iters = 2 needs one buffer, iters = 1 none
+  const int rc = carve(ws, ws_bytes, std::min(iters - 1, 2), n * ld_w * 4, &carved);
+  if (rc) return rc;
+  void* const* w = carved.buf;
   const int64_t lds[3] = {ld_h, ld_z, ld_w};
   const void* ptrs[4] = {H, Z, w[0], w[1]};
   const int V = appnp::pick_vec(APPNP_F32, f, lds, 3, ptrs, 4);
@@ -745,10 +739,8 @@ int solve_loop(StepArgs a, const void* H, int64_t ld_h, void* Z, int64_t ld_z, i
       a.ld_aux = k == 2 ? ld_h : ld_w;
       a.omega = (float)omega;
     }
-    ktimer_begin(s);
-    const int rc = dev_err(appnp::launch_step(APPNP_F32, epi, V, a, s));
-    ktimer_mark(s, APPNP_KT_STEP);
-    if (rc) return rc;
+    const int step_rc = timed_step(APPNP_F32, epi, V, a, s);
+    if (step_rc) return step_rc;
     src = dst;
     ld_src = ld_dst;
   }
@@ -819,15 +811,7 @@ int appnp_solve_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, void* d
   if (rc || !run) return rc;
   // Pi^T = alpha (I - (1-alpha) A_hat^T)^-1: the same solve on A_hat^T, whose spectrum is A_hat's
   StepArgs a = base_args(g, f, alpha);
-  if (g->mode != APPNP_NORM_SYM) {
-    a.row_ptr = g->t_row_ptr;
-    a.col = g->t_col;
-    a.val = g->t_val;
-    a.heavy = g->t_heavy;
-    a.n_heavy = g->t_n_heavy;
-    a.hub = g->t_hub;
-    a.n_hub = g->t_n_hub;
-  }
+  if (g->mode != APPNP_NORM_SYM) use_transpose(a, g);
   return solve_loop(a, dZ, ld_dz, dH, ld_dh, f, iters, alpha, ws, ws_bytes, as_stream(stream));
 }
 
@@ -861,6 +845,182 @@ int appnp_spmm(const int32_t* indptr, const int32_t* indices, const float* vals,
   return dev_err(appnp::launch_step(APPNP_F32, appnp::EPI_PARTIAL, V, a, as_stream(stream)));
 }
 
+// ---- per-iteration steps ------------------------------------------------------------------
+//
+// appnp_step, appnp_step_split, appnp_step_shards and appnp_step_split_shards are one operation:
+// the SpMM step over some of the held rows' entries, in one of four roles -- produce a partial
+// (SHARDS_FIRST, PART_LOCAL), add to it (SHARDS_ACC), finish the row from it (SHARDS_LAST,
+// PART_REMOTE), or do the whole row (SHARDS_ONLY, PART_ALL).  Each entry point keeps its own
+// early checks and operand names; which entries it multiplies, and in which role, is a StepPart.
+
+namespace {
+
+struct StepPart {
+  const int32_t* row_ptr;
+  const int32_t* row_end;  // null: row i's entries end at row_ptr[i + 1]
+  const int32_t* col;
+  const float* val;
+  int64_t nnz;         // the entries (of a shard range: its uniform share): picks the row shape
+  bool whole;          // every entry of the held rows, so their heavy / hub lists apply
+  int epi;
+  int kind;            // APPNP_KT_* of the step's launch
+  bool to_partial;     // the product goes to the fp32 partial: no H yet, no output row
+  bool reads_partial;  // the product continues from the partial
+  bool finishes() const { return !to_partial; }  // the output row: + alpha H
+};
+
+// The entries of `part` (appnp_part): the held rows' CSR, or its local / remote half.
+int part_of(const appnp_graph* g, int part, int dtype, StepPart* p) {
+  *p = StepPart{g->row_ptr, nullptr, g->col, g->val, g->nnz_hat, true,
+                appnp::EPI_FWD, APPNP_KT_STEP, false, false};
+  if (part == APPNP_PART_ALL) return APPNP_OK;
+  if (!g->split) return APPNP_EINVAL;
+  if (dtype != APPNP_F32) return APPNP_ENOTSUP;
+  if (part == APPNP_PART_LOCAL)
+    *p = StepPart{g->lrow_ptr, nullptr, g->lcol, g->lval, g->nnz_local, false,
+                  appnp::EPI_PARTIAL, APPNP_KT_LOCAL, true, false};
+  else if (part == APPNP_PART_REMOTE)
+    *p = StepPart{g->rrow_ptr, nullptr, g->rcol, g->rval, g->nnz_remote, false,
+                  appnp::EPI_FINISH, APPNP_KT_REMOTE, false, true};
+  else
+    return APPNP_EINVAL;
+  return APPNP_OK;
+}
+
+// The held rows' entries with a column in shards [s_lo, s_hi), in the role of `mode`
+// (appnp_shard_mode): FIRST partial = y, ACC partial += y, LAST out = y + partial + alpha H,
+// ONLY out = y + alpha H.
+int shards_of(const appnp_graph* g, int s_lo, int s_hi, int mode, StepPart* p) {
+  if (!g->sh_off) return APPNP_EINVAL;  // appnp_graph_shard_offsets first
+  if (s_lo < 0 || s_hi > g->sh_n || s_lo >= s_hi) return APPNP_EINVAL;
+  const int64_t rows = g->row_hi - g->row_lo;
+  // the kernel shape follows the average row length: the range's share of the entries
+  *p = StepPart{g->sh_off + (int64_t)s_lo * rows, g->sh_off + (int64_t)s_hi * rows, g->col,
+                g->val, g->nnz_hat * (int64_t)(s_hi - s_lo) / g->sh_n, false,
+                appnp::EPI_FWD, APPNP_KT_REMOTE, false, false};
+  switch (mode) {
+    case APPNP_SHARDS_FIRST:
+      p->epi = appnp::EPI_PARTIAL;
+      p->kind = APPNP_KT_LOCAL;
+      p->to_partial = true;
+      return APPNP_OK;
+    case APPNP_SHARDS_ACC:
+      p->epi = appnp::EPI_ACCUM;
+      p->to_partial = p->reads_partial = true;
+      return APPNP_OK;
+    case APPNP_SHARDS_LAST:
+      p->epi = appnp::EPI_FINISH;
+      p->reads_partial = true;
+      return APPNP_OK;
+    case APPNP_SHARDS_ONLY: return APPNP_OK;
+    default: return APPNP_EINVAL;
+  }
+}
+
+// base_args over the entries of `p`, with iteration k's dropout
+StepArgs part_args(const appnp_graph* g, const StepPart& p, int64_t f, int k, float alpha,
+                   float p_drop, uint64_t seed) {
+  StepArgs a = base_args(g, f, alpha);
+  a.row_ptr = p.row_ptr;
+  a.row_end = p.row_end;
+  a.col = p.col;
+  a.val = p.val;
+  a.nnz = p.nnz;
+  if (!p.whole) drop_row_lists(a);
+  set_drop(a, p_drop, seed, k);
+  return a;
+}
+
+// What a whole-row step reads beside Zin: H where it finishes the row, the partial where it
+// continues from one
+int check_reads(const StepPart& p, const void* H, int64_t ld_h, const float* partial,
+                int64_t ld_partial, int64_t f) {
+  if (p.finishes() && (!H || ld_h < f)) return APPNP_EINVAL;
+  if (p.reads_partial && (!partial || ld_partial < f)) return APPNP_EINVAL;
+  return APPNP_OK;
+}
+
+// The whole-row step of `p` at vector width V, into `out`: the caller's output rows, or its
+// partial where p.to_partial.
+int step_rows(const appnp_graph* g, const StepPart& p, int dtype, int V, const void* Zin,
+              int64_t ld_in, const void* H, int64_t ld_h, void* out, int64_t ld_out,
+              const float* partial, int64_t ld_partial, int64_t f, int k, float alpha,
+              float p_drop, uint64_t seed, hipStream_t s) {
+  StepArgs a = part_args(g, p, f, k, alpha, p_drop, seed);
+  a.zin = Zin;
+  a.ld_in = ld_in;
+  a.out = out;
+  a.ld_out = ld_out;
+  if (p.finishes()) {
+    a.h = H;
+    a.ld_h = ld_h;
+    if (p.reads_partial) {
+      a.aux = const_cast<float*>(partial);
+      a.ld_aux = ld_partial;
+    }
+  }
+  return timed_step(dtype, p.epi, V, a, s, p.kind);
+}
+
+// remainder columns of a held-rows split step (appnp_step_split / appnp_split_copy); 0: none
+int64_t rows_split(const appnp_graph* g, int64_t f) {
+  return g ? remainder_cols(g, f, APPNP_F32, true) : 0;
+}
+
+// The step of `p` in the split layout of the held rows (remainder columns r): the main launch
+// on the fs = f - r main columns, then, where p finishes the row, the remainder pass.
+int step_split_rows(const appnp_graph* g, const StepPart& p, int64_t r, const float* zin_main,
+                    const float* zin_rem, const float* H, int64_t ld_h, float* zout_main,
+                    float* zout_rem, float* Z, int64_t ld_z, float* partial, int64_t ld_partial,
+                    int64_t f, int k, float alpha, float p_drop, uint64_t seed, hipStream_t s) {
+  const int64_t fs = f - r, rw = 4 * (int64_t)g->rb_lpe;
+  const bool to_z = Z != nullptr;
+  const bool uses_partial = p.to_partial || p.reads_partial;
+  // inputs: every row of both parts (the remainder only where the pass runs)
+  if (fs > 0 && !zin_main) return APPNP_EINVAL;
+  if (p.finishes() && (!zin_rem || !H || ld_h < f)) return APPNP_EINVAL;
+  if (p.finishes() && !to_z && (!zout_rem || (fs > 0 && !zout_main))) return APPNP_EINVAL;
+  if (to_z && ld_z < f) return APPNP_EINVAL;
+  if (uses_partial && (!partial || ld_partial < fs)) return APPNP_EINVAL;
+  const int64_t lds[3] = {p.finishes() ? ld_h : 4, to_z ? ld_z : 4, uses_partial ? ld_partial : 4};
+  const void* ptrs[7] = {zin_main, zin_rem, H, zout_main, zout_rem, Z, partial};
+  if (!vec16(lds, 3, ptrs, 7)) return APPNP_EINVAL;
+  if (fs > 0) {
+    StepArgs am = part_args(g, p, fs, k, alpha, p_drop, seed);
+    am.zin = zin_main;
+    am.ld_in = fs;
+    if (p.to_partial) {
+      am.out = partial;
+      am.ld_out = ld_partial;
+    } else {
+      am.out = to_z ? Z : zout_main + g->row_lo * fs;
+      am.ld_out = to_z ? ld_z : fs;
+      am.h = H;
+      am.ld_h = ld_h;
+      if (p.reads_partial) {
+        am.aux = partial;
+        am.ld_aux = ld_partial;
+      }
+    }
+    const int rc = timed_step(APPNP_F32, p.epi, 4, am, s, p.kind);
+    if (rc) return rc;
+  }
+  if (!p.finishes()) return APPNP_OK;  // the pass needs every row of zin_rem
+  // the remainder pass over every source block: into the next remainder buffer at the held
+  // rows (a unit graph stores dr o y there), or into Z's last r columns
+  StepArgs a = base_args(g, f, alpha);
+  set_drop(a, p_drop, seed, k);
+  const int nv = (g->rb_lpe == 1 && !to_z) ? 4 : (int)r;
+  g->rem_launches.fetch_add(1, std::memory_order_relaxed);
+  return timed(s, APPNP_KT_REM, [&] {
+    return appnp::launch_remainder(g, a, appnp::EPI_FWD, zin_rem, H + fs, ld_h,
+                                   to_z ? Z + fs : zout_rem + g->row_lo * rw, to_z ? ld_z : rw,
+                                   nv, !to_z, s);
+  });
+}
+
+}  // namespace
+
 int appnp_step(const appnp_graph* g, int part, const void* Zin, int64_t ld_in, const void* H,
                int64_t ld_h, void* Zout, int64_t ld_out, const float* partial,
                int64_t ld_partial, int64_t f, int dtype, int k, float alpha, float p_drop,
@@ -868,70 +1028,22 @@ int appnp_step(const appnp_graph* g, int part, const void* Zin, int64_t ld_in, c
   int rc = check_common(g, f, dtype, 0, alpha, p_drop);
   if (rc) return rc;
   if (k < 0) return APPNP_EINVAL;
-  const int64_t rows = g->row_hi - g->row_lo;
-  if (rows == 0 || f == 0) return APPNP_OK;
+  if (g->row_hi == g->row_lo || f == 0) return APPNP_OK;
   if (!Zin || !Zout || ld_in < f || ld_out < f) return APPNP_EINVAL;
-  StepArgs a = base_args(g, f, alpha);
-  a.zin = Zin;
-  a.ld_in = ld_in;
-  a.out = Zout;
-  a.ld_out = ld_out;
-  set_drop(a, p_drop, seed, k);
-  int epi = appnp::EPI_FWD;
-  int64_t lds[4] = {ld_in, ld_out, ld_h, ld_partial};
+  StepPart p;
+  if ((rc = part_of(g, part, dtype, &p))) return rc;
+  if ((rc = check_reads(p, H, ld_h, partial, ld_partial, f))) return rc;
+  // every pointer counts whatever the part reads, the leading dimensions only of what it reads;
+  // PART_LOCAL's partial is Zout
+  const int64_t lds[4] = {ld_in, ld_out, ld_h, ld_partial};
   const void* ptrs[4] = {Zin, Zout, H, partial};
-  int n_ld = 2;
-  if (part == APPNP_PART_ALL) {
-    if (!H || ld_h < f) return APPNP_EINVAL;
-    a.h = H;
-    a.ld_h = ld_h;
-    n_ld = 3;
-  } else {
-    if (!g->split) return APPNP_EINVAL;
-    if (dtype != APPNP_F32) return APPNP_ENOTSUP;
-    a.heavy = nullptr;  // the heavy/hub lists describe the full rows, not their halves
-    a.n_heavy = 0;
-    a.hub = nullptr;
-    a.n_hub = 0;
-    if (part == APPNP_PART_LOCAL) {
-      epi = appnp::EPI_PARTIAL;
-      a.nnz = g->nnz_local;
-      a.row_ptr = g->lrow_ptr;
-      a.col = g->lcol;
-      a.val = g->lval;
-    } else if (part == APPNP_PART_REMOTE) {
-      if (!H || ld_h < f || !partial || ld_partial < f) return APPNP_EINVAL;
-      epi = appnp::EPI_FINISH;
-      a.nnz = g->nnz_remote;
-      a.row_ptr = g->rrow_ptr;
-      a.col = g->rcol;
-      a.val = g->rval;
-      a.h = H;
-      a.ld_h = ld_h;
-      a.aux = const_cast<float*>(partial);
-      a.ld_aux = ld_partial;
-      n_ld = 4;
-    } else {
-      return APPNP_EINVAL;
-    }
-  }
+  const int n_ld = p.reads_partial ? 4 : p.finishes() ? 3 : 2;
   const int V = appnp::pick_vec(dtype, f, lds, n_ld, ptrs, 4);
-  ktimer_begin(as_stream(stream));
-  rc = dev_err(appnp::launch_step(dtype, epi, V, a, as_stream(stream)));
-  ktimer_mark(as_stream(stream), part_kind(part));
-  return rc;
+  return step_rows(g, p, dtype, V, Zin, ld_in, H, ld_h, Zout, ld_out, partial, ld_partial, f, k,
+                   alpha, p_drop, seed, as_stream(stream));
 }
 
 // ---- the split layout on the held rows of a row-partitioned graph -------------------------
-
-namespace {
-
-// remainder columns of a held-rows split step (appnp_step_split / appnp_split_copy); 0: none
-int64_t rows_split(const appnp_graph* g, int64_t f) {
-  return g ? remainder_cols(g, f, APPNP_F32, true) : 0;
-}
-
-}  // namespace
 
 int appnp_split_layout(const appnp_graph* g, int64_t f, int64_t* fs, int64_t* rem_width) {
   if (!g || f < 0) return APPNP_EINVAL;
@@ -952,14 +1064,12 @@ int appnp_split_copy(const appnp_graph* g, const float* H, int64_t ld_h, int64_t
   const void* ptrs[3] = {H, main, rem};
   if (!H || !rem || (fs > 0 && !main) || ld_h < f || !vec16(lds, 1, ptrs, 3)) return APPNP_EINVAL;
   const float* sc = appnp::remainder_scale(g);
-  ktimer_begin(as_stream(stream));
-  const int rc = dev_err(appnp::launch_split_copy(H, ld_h, rows, f, fs, rw,
-                                                  main ? main + g->row_lo * fs : nullptr,
-                                                  rem + g->row_lo * rw,
-                                                  sc ? sc + g->row_lo : nullptr,
-                                                  as_stream(stream)));
-  ktimer_mark(as_stream(stream), APPNP_KT_COPY);
-  return rc;
+  const hipStream_t s = as_stream(stream);
+  return timed(s, APPNP_KT_COPY, [&] {
+    return appnp::launch_split_copy(H, ld_h, rows, f, fs, rw,
+                                    main ? main + g->row_lo * fs : nullptr, rem + g->row_lo * rw,
+                                    sc ? sc + g->row_lo : nullptr, s);
+  });
 }
 
 int appnp_step_split(const appnp_graph* g, int part, const float* zin_main, const float* zin_rem,
@@ -971,77 +1081,12 @@ int appnp_step_split(const appnp_graph* g, int part, const float* zin_main, cons
   if (k < 0 || part < APPNP_PART_ALL || part > APPNP_PART_REMOTE) return APPNP_EINVAL;
   const int64_t r = rows_split(g, f);
   if (!r) return APPNP_ENOTSUP;
-  const int64_t rows = g->row_hi - g->row_lo, fs = f - r, rw = 4 * (int64_t)g->rb_lpe;
-  if (rows == 0 || f == 0) return APPNP_OK;
-  if (part != APPNP_PART_ALL && (!g->split || fs == 0)) return APPNP_EINVAL;
-  const bool to_z = Z != nullptr;
-  // inputs: every row of both parts (the remainder only where the pass runs)
-  if (fs > 0 && !zin_main) return APPNP_EINVAL;
-  if (part != APPNP_PART_LOCAL && !zin_rem) return APPNP_EINVAL;
-  if (part != APPNP_PART_LOCAL && (!H || ld_h < f)) return APPNP_EINVAL;
-  if (part != APPNP_PART_LOCAL && !to_z && (!zout_rem || (fs > 0 && !zout_main)))
-    return APPNP_EINVAL;
-  if (to_z && ld_z < f) return APPNP_EINVAL;
-  if (part != APPNP_PART_ALL && (!partial || ld_partial < fs)) return APPNP_EINVAL;
-  const int64_t lds[3] = {part != APPNP_PART_LOCAL ? ld_h : 4, to_z ? ld_z : 4,
-                          part != APPNP_PART_ALL ? ld_partial : 4};
-  const void* ptrs[8] = {zin_main, zin_rem, H, zout_main, zout_rem, Z, partial, nullptr};
-  if (!vec16(lds, 3, ptrs, 7)) return APPNP_EINVAL;
-  const hipStream_t s = as_stream(stream);
-  StepArgs a = base_args(g, f, alpha);
-  set_drop(a, p_drop, seed, k);
-  if (fs > 0) {
-    StepArgs am = a;
-    am.f = (int32_t)fs;
-    am.zin = zin_main;
-    am.ld_in = fs;
-    am.out = to_z ? static_cast<void*>(Z) : static_cast<void*>(zout_main + g->row_lo * fs);
-    am.ld_out = to_z ? ld_z : fs;
-    int epi = appnp::EPI_FWD;
-    if (part == APPNP_PART_ALL) {
-      am.h = H;
-      am.ld_h = ld_h;
-    } else {
-      am.heavy = nullptr;  // the heavy / hub lists describe the full rows, not their halves
-      am.n_heavy = 0;
-      am.hub = nullptr;
-      am.n_hub = 0;
-      if (part == APPNP_PART_LOCAL) {
-        epi = appnp::EPI_PARTIAL;
-        am.nnz = g->nnz_local;
-        am.row_ptr = g->lrow_ptr;
-        am.col = g->lcol;
-        am.val = g->lval;
-        am.out = partial;
-        am.ld_out = ld_partial;
-      } else {
-        epi = appnp::EPI_FINISH;
-        am.nnz = g->nnz_remote;
-        am.row_ptr = g->rrow_ptr;
-        am.col = g->rcol;
-        am.val = g->rval;
-        am.h = H;
-        am.ld_h = ld_h;
-        am.aux = partial;
-        am.ld_aux = ld_partial;
-      }
-    }
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_step(APPNP_F32, epi, 4, am, s));
-    ktimer_mark(s, part_kind(part));
-    if (rc) return rc;
-  }
-  if (part == APPNP_PART_LOCAL) return APPNP_OK;  // the pass needs every row of zin_rem
-  // the remainder pass over every source block: into the next remainder buffer at the held
-  // rows (a unit graph stores dr o y there), or into Z's last r columns
-  const int nv = (g->rb_lpe == 1 && !to_z) ? 4 : (int)r;
-  g->rem_launches.fetch_add(1, std::memory_order_relaxed);
-  ktimer_begin(s);
-  rc = dev_err(appnp::launch_remainder(g, a, appnp::EPI_FWD, zin_rem, H + fs, ld_h,
-                                       to_z ? Z + fs : zout_rem + g->row_lo * rw,
-                                       to_z ? ld_z : rw, nv, !to_z, s));
-  ktimer_mark(s, APPNP_KT_REM);
-  return rc;
+  if (g->row_hi == g->row_lo || f == 0) return APPNP_OK;
+  StepPart p;
+  if ((rc = part_of(g, part, APPNP_F32, &p))) return rc;
+  if (part != APPNP_PART_ALL && r == f) return APPNP_EINVAL;  // no main columns to halve
+  return step_split_rows(g, p, r, zin_main, zin_rem, H, ld_h, zout_main, zout_rem, Z, ld_z,
+                         partial, ld_partial, f, k, alpha, p_drop, seed, as_stream(stream));
 }
 
 // ---- pipelined row steps: the held rows' entries of a range of source shards -------------
@@ -1051,38 +1096,6 @@ int appnp_graph_shard_offsets(appnp_graph* g, int nshards, int64_t shard_rows, v
   return appnp::graph_build_shard_offsets(g, nshards, shard_rows, as_stream(stream));
 }
 
-namespace {
-
-// The step's CSR restricted to the held rows' entries with a column in shards [s_lo, s_hi), and
-// the epilogue of `mode` (appnp_shard_mode): FIRST partial = y, ACC partial += y, LAST out = y +
-// partial + alpha H, ONLY out = y + alpha H.  Returns APPNP_OK or a code.
-int shard_step_args(const appnp_graph* g, int s_lo, int s_hi, int mode, StepArgs& a, int* epi) {
-  if (!g->sh_off) return APPNP_EINVAL;  // appnp_graph_shard_offsets first
-  if (s_lo < 0 || s_hi > g->sh_n || s_lo >= s_hi) return APPNP_EINVAL;
-  const int64_t rows = g->row_hi - g->row_lo;
-  a.row_ptr = g->sh_off + (int64_t)s_lo * rows;
-  a.row_end = g->sh_off + (int64_t)s_hi * rows;
-  // the kernel shape follows the average row length: the range's share of the entries
-  a.nnz = g->nnz_hat * (int64_t)(s_hi - s_lo) / g->sh_n;
-  a.heavy = nullptr;  // the heavy / hub lists describe whole rows, not their shard ranges
-  a.n_heavy = 0;
-  a.hub = nullptr;
-  a.n_hub = 0;
-  switch (mode) {
-    case APPNP_SHARDS_FIRST: *epi = appnp::EPI_PARTIAL; return APPNP_OK;
-    case APPNP_SHARDS_ACC: *epi = appnp::EPI_ACCUM; return APPNP_OK;
-    case APPNP_SHARDS_LAST: *epi = appnp::EPI_FINISH; return APPNP_OK;
-    case APPNP_SHARDS_ONLY: *epi = appnp::EPI_FWD; return APPNP_OK;
-    default: return APPNP_EINVAL;
-  }
-}
-
-inline int shard_kind(int mode) {
-  return mode == APPNP_SHARDS_FIRST ? APPNP_KT_LOCAL : APPNP_KT_REMOTE;
-}
-
-}  // namespace
-
 int appnp_step_shards(const appnp_graph* g, int s_lo, int s_hi, int mode, const float* Zin,
                       int64_t ld_in, const float* H, int64_t ld_h, float* Zout, int64_t ld_out,
                       float* partial, int64_t ld_partial, int64_t f, int k, float alpha,
@@ -1090,41 +1103,21 @@ int appnp_step_shards(const appnp_graph* g, int s_lo, int s_hi, int mode, const 
   int rc = check_common(g, f, APPNP_F32, 0, alpha, p_drop);
   if (rc) return rc;
   if (k < 0) return APPNP_EINVAL;
-  const int64_t rows = g->row_hi - g->row_lo;
-  StepArgs a = base_args(g, f, alpha);
-  int epi = appnp::EPI_FWD;
-  rc = shard_step_args(g, s_lo, s_hi, mode, a, &epi);
-  if (rc) return rc;
-  if (rows == 0 || f == 0) return APPNP_OK;
-  const bool to_partial = mode == APPNP_SHARDS_FIRST || mode == APPNP_SHARDS_ACC;
-  const bool reads_partial = mode == APPNP_SHARDS_ACC || mode == APPNP_SHARDS_LAST;
-  const bool reads_h = mode == APPNP_SHARDS_LAST || mode == APPNP_SHARDS_ONLY;
-  if (!Zin || ld_in < f) return APPNP_EINVAL;
-  if ((to_partial || reads_partial) && (!partial || ld_partial < f)) return APPNP_EINVAL;
-  if (!to_partial && (!Zout || ld_out < f)) return APPNP_EINVAL;
-  if (reads_h && (!H || ld_h < f)) return APPNP_EINVAL;
-  a.zin = Zin;
-  a.ld_in = ld_in;
-  a.out = to_partial ? static_cast<void*>(partial) : static_cast<void*>(Zout);
-  a.ld_out = to_partial ? ld_partial : ld_out;
-  if (reads_h) {
-    a.h = H;
-    a.ld_h = ld_h;
-  }
-  if (mode == APPNP_SHARDS_LAST) {
-    a.aux = partial;
-    a.ld_aux = ld_partial;
-  }
-  set_drop(a, p_drop, seed, k);
-  const int64_t lds[4] = {ld_in, a.ld_out, reads_h ? ld_h : ld_in,
-                          reads_partial ? ld_partial : ld_in};
-  const void* ptrs[4] = {Zin, a.out, reads_h ? H : nullptr, reads_partial ? partial : nullptr};
+  StepPart p;
+  if ((rc = shards_of(g, s_lo, s_hi, mode, &p))) return rc;
+  if (g->row_hi == g->row_lo || f == 0) return APPNP_OK;
+  // FIRST / ACC write the partial, LAST / ONLY the output rows
+  void* const out = p.to_partial ? static_cast<void*>(partial) : static_cast<void*>(Zout);
+  const int64_t ld = p.to_partial ? ld_partial : ld_out;
+  if (!Zin || ld_in < f || !out || ld < f) return APPNP_EINVAL;
+  if ((rc = check_reads(p, H, ld_h, partial, ld_partial, f))) return rc;
+  const int64_t lds[4] = {ld_in, ld, p.finishes() ? ld_h : ld_in,
+                          p.reads_partial ? ld_partial : ld_in};
+  const void* ptrs[4] = {Zin, out, p.finishes() ? H : nullptr,
+                         p.reads_partial ? partial : nullptr};
   const int V = appnp::pick_vec(APPNP_F32, f, lds, 4, ptrs, 4);
-  const hipStream_t s = as_stream(stream);
-  ktimer_begin(s);
-  rc = dev_err(appnp::launch_step(APPNP_F32, epi, V, a, s));
-  ktimer_mark(s, shard_kind(mode));
-  return rc;
+  return step_rows(g, p, APPNP_F32, V, Zin, ld_in, H, ld_h, out, ld, partial, ld_partial, f, k,
+                   alpha, p_drop, seed, as_stream(stream));
 }
 
 int appnp_step_split_shards(const appnp_graph* g, int s_lo, int s_hi, int mode,
@@ -1137,61 +1130,12 @@ int appnp_step_split_shards(const appnp_graph* g, int s_lo, int s_hi, int mode,
   if (k < 0) return APPNP_EINVAL;
   const int64_t r = rows_split(g, f);
   if (!r) return APPNP_ENOTSUP;
-  const int64_t rows = g->row_hi - g->row_lo, fs = f - r, rw = 4 * (int64_t)g->rb_lpe;
-  StepArgs a = base_args(g, f, alpha);
-  StepArgs am = a;
-  int epi = appnp::EPI_FWD;
-  rc = shard_step_args(g, s_lo, s_hi, mode, am, &epi);
-  if (rc) return rc;
-  if (rows == 0 || f == 0) return APPNP_OK;
-  const bool to_partial = mode == APPNP_SHARDS_FIRST || mode == APPNP_SHARDS_ACC;
-  const bool reads_partial = mode == APPNP_SHARDS_ACC || mode == APPNP_SHARDS_LAST;
-  const bool finishes = !to_partial;  // LAST / ONLY: the row's output, then the remainder pass
-  const bool to_z = Z != nullptr;
-  if (fs == 0 && mode != APPNP_SHARDS_ONLY) return APPNP_EINVAL;  // nothing to pipeline
-  if (fs > 0 && !zin_main) return APPNP_EINVAL;
-  if (finishes && (!zin_rem || !H || ld_h < f)) return APPNP_EINVAL;
-  if (finishes && !to_z && (!zout_rem || (fs > 0 && !zout_main))) return APPNP_EINVAL;
-  if (to_z && ld_z < f) return APPNP_EINVAL;
-  if ((to_partial || reads_partial) && (!partial || ld_partial < fs)) return APPNP_EINVAL;
-  const int64_t lds[3] = {finishes ? ld_h : 4, to_z ? ld_z : 4,
-                          (to_partial || reads_partial) ? ld_partial : 4};
-  const void* ptrs[8] = {zin_main, zin_rem, H, zout_main, zout_rem, Z, partial, nullptr};
-  if (!vec16(lds, 3, ptrs, 7)) return APPNP_EINVAL;
-  const hipStream_t s = as_stream(stream);
-  set_drop(a, p_drop, seed, k);
-  set_drop(am, p_drop, seed, k);
-  if (fs > 0) {
-    am.f = (int32_t)fs;
-    am.zin = zin_main;
-    am.ld_in = fs;
-    if (to_partial) {
-      am.out = partial;
-      am.ld_out = ld_partial;
-    } else {
-      am.out = to_z ? static_cast<void*>(Z) : static_cast<void*>(zout_main + g->row_lo * fs);
-      am.ld_out = to_z ? ld_z : fs;
-      am.h = H;
-      am.ld_h = ld_h;
-      if (reads_partial) {
-        am.aux = partial;
-        am.ld_aux = ld_partial;
-      }
-    }
-    ktimer_begin(s);
-    rc = dev_err(appnp::launch_step(APPNP_F32, epi, 4, am, s));
-    ktimer_mark(s, shard_kind(mode));
-    if (rc) return rc;
-  }
-  if (!finishes) return APPNP_OK;  // the pass needs every row of zin_rem
-  const int nv = (g->rb_lpe == 1 && !to_z) ? 4 : (int)r;
-  g->rem_launches.fetch_add(1, std::memory_order_relaxed);
-  ktimer_begin(s);
-  rc = dev_err(appnp::launch_remainder(g, a, appnp::EPI_FWD, zin_rem, H + fs, ld_h,
-                                       to_z ? Z + fs : zout_rem + g->row_lo * rw,
-                                       to_z ? ld_z : rw, nv, !to_z, s));
-  ktimer_mark(s, APPNP_KT_REM);
-  return rc;
+  StepPart p;
+  if ((rc = shards_of(g, s_lo, s_hi, mode, &p))) return rc;
+  if (g->row_hi == g->row_lo || f == 0) return APPNP_OK;
+  if (r == f && mode != APPNP_SHARDS_ONLY) return APPNP_EINVAL;  // nothing to pipeline
+  return step_split_rows(g, p, r, zin_main, zin_rem, H, ld_h, zout_main, zout_rem, Z, ld_z,
+                         partial, ld_partial, f, k, alpha, p_drop, seed, as_stream(stream));
 }
 
 // ---- the per-launch timer (measurement aid; include/ppnp_amd.h) ----------------------------
