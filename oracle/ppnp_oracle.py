@@ -18,6 +18,9 @@ operator that the HIP path replaces:
 * ``edge_keep_mask``  -- the counter-hash edge-dropout mask the HIP kernel uses (no reference
                          oracle exists for edge dropout; this pins the
                          device mask bit-for-bit instead)
+* ``round_bf16`` / ``step_exact`` / ``close_bf16_step`` / ``envelope`` -- the bf16 storage
+                         reference: one step of the kernel must land within half a bf16 spacing
+                         of the exact result plus an fp32 accumulation bound, element by element
 
 Parity pin: ``tests/test_oracle.py`` checks every function above against the golden vectors
 in ``tests/golden/*.npz``, which ``tests/golden/make_golden.py`` produced by importing the
@@ -315,3 +318,124 @@ def synth_graph(n_nodes: int, n_edges: int, seed: int):
     a.eliminate_zeros()
     a.sort_indices()
     return a.astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------
+# bf16 storage reference: what one step of the kernel may store, element by element
+# --------------------------------------------------------------------------------------
+#
+# The kernel computes t = s * sum_j w_ij z_j + a * h_i in fp32 along some summation order, so
+# its value before the store is within the standard (d + 2) 2^-24 S of the exact t, with
+# S = s * sum_j |w_ij| |z_j| + a |h_i| and d the stored entries of the row.  ``delta`` is that
+# with more than 2x headroom, (d + 8) 2^-23 S, which also leaves room for the fp32 dropout scale
+# and the adjoint's extra factor.  Round-to-nearest-even then adds at most half a bf16 spacing of
+# the value rounded, which lies within delta of t.  No figure here is measured on a device.
+
+
+def round_bf16(x):
+    """float32 -> float32 holding bf16 values: round to nearest even, NaN kept (quiet).  The
+    integer trick of ``f32_to_bf16`` in ppnp_amd/csrc/appnp_device.h."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    with np.errstate(over="ignore"):
+        r = (u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)
+    r = np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), r).astype(np.uint32)
+    return (r << np.uint32(16)).view(np.float32).reshape(x.shape)
+
+
+def spacing_bf16(x):
+    """2^(floor(log2(max(|x|, 2^-126))) - 7): the distance between neighbouring bf16 values in
+    the binade of x (fp64)."""
+    ax = np.maximum(np.abs(np.asarray(x, dtype=np.float64)), 2.0 ** -126)
+    _, e = np.frexp(ax)  # ax = m 2^e with m in [0.5, 1): floor(log2 ax) = e - 1
+    return np.ldexp(1.0, e - 1 - 7)
+
+
+def _step_operator(indptr, indices, w32, alpha, k, p_drop, seed, transposed, h_weight,
+                   y_weight, row_lo=0):
+    """The fp32 quantities of one kernel step, held in fp64: (indptr, indices, kept weights),
+    s and a.  The dropout mask is keyed on global rows: row_lo + local row."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    indices = np.asarray(indices, dtype=np.int64)
+    w = np.asarray(w32, dtype=np.float32)
+    rows = np.repeat(np.arange(indptr.size - 1, dtype=np.int64), np.diff(indptr)) + row_lo
+    if p_drop > 0.0:
+        keep = (edge_keep_mask(indices, rows, k, p_drop, seed) if transposed
+                else edge_keep_mask(rows, indices, k, p_drop, seed))
+        scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p_drop))
+        w = np.where(keep, (w * scale).astype(np.float32), np.float32(0.0))
+    s = float(np.float32(1.0) - np.float32(alpha))
+    if y_weight is not None:
+        s *= float(np.float32(y_weight))
+    a = float(np.float32(alpha if h_weight is None else h_weight))
+    return indptr, indices, w.astype(np.float64), s, a
+
+
+def step_exact(indptr, indices, w32, Zin, H, alpha, k, p_drop, seed, transposed=False,
+               h_weight=None, y_weight=None, row_lo=0):
+    """One step of the kernel in exact arithmetic on the kernel's own fp32 operands.
+
+    Returns (t, delta), fp64: t_i = s sum_j w_ij z_j + a h_i and delta_i = (d_i + 8) 2^-23 S_i,
+    S_i = s sum_j |w_ij| |z_j| + a |h_i|, d_i the stored entries of row i.  s = float32(1) -
+    float32(alpha) evaluated in fp32 as the library does, a = float32(alpha); ``w32`` are the
+    fp32 A_hat values (``Graph.csr()``).  Under dropout the kept weights are float32(w32 *
+    float32(1 / (1 - p))) with the mask of ``edge_keep_mask``; ``transposed`` keys entry (i, j)
+    as (j, i) (the adjoint's rows are the forward's columns).  ``h_weight`` overrides a (the
+    adjoint's last step adds dH with weight 1), ``y_weight`` multiplies s (the adjoint's earlier
+    steps add alpha y to dH).  ``H`` may be None (a partial product).  ``row_lo``: global index
+    of row 0 of ``indptr`` (the mask is keyed on global rows)."""
+    indptr, indices, w, s, a = _step_operator(indptr, indices, w32, alpha, k, p_drop, seed,
+                                              transposed, h_weight, y_weight, row_lo)
+    Z = np.asarray(Zin, dtype=np.float64)
+    n_rows = indptr.size - 1
+    W = sp.csr_matrix((w, indices, indptr), shape=(n_rows, Z.shape[0]))
+    t = s * (W @ Z)
+    S = s * (abs(W) @ np.abs(Z))
+    if H is not None:
+        h = np.asarray(H, dtype=np.float64)
+        t = t + a * h
+        S = S + abs(a) * np.abs(h)
+    d = np.diff(indptr).astype(np.float64)[:, None]
+    return t, (d + 8.0) * 2.0 ** -23 * S
+
+
+def close_bf16_step(out, t, delta, label=""):
+    """Assert |out - t| <= 0.5 spacing_bf16(|t| + delta) + delta for every element; print and
+    return (worst ratio, share of elements bit-equal to round_bf16(t))."""
+    out = np.asarray(out, dtype=np.float64)
+    bound = 0.5 * spacing_bf16(np.abs(t) + delta) + delta
+    ratio = np.abs(out - t) / bound
+    worst = float(ratio.max()) if ratio.size else 0.0
+    rne = round_bf16(t.astype(np.float32)).astype(np.float64)
+    share = float((out == rne).mean()) if out.size else 1.0
+    over = int((~(ratio <= 1.0)).sum())  # a NaN in out counts as over
+    print(f"bf16 step {label}: worst ratio {worst:.4f}, over the bound {over} of {out.size}, "
+          f"bit-equal to RNE(t) {100.0 * share:.3f} %")
+    if over:
+        bad = np.argwhere(~(ratio <= 1.0))
+        where = ", ".join(f"{tuple(i)} got {out[tuple(i)]:.6g} exact {t[tuple(i)]:.6g}"
+                          for i in bad[:6])
+        raise AssertionError(
+            f"{over} of {out.size} elements beyond half a bf16 spacing + delta (worst ratio "
+            f"{worst:.4f}) {label}: {len(set(bad[:, 0].tolist()))} rows, columns "
+            f"{sorted(set(bad[:, -1].tolist()))[:16]}; {where}")
+    return worst, share
+
+
+def envelope(indptr, indices, w32, E_prev, E_h, t, delta, alpha, k=0, p_drop=0.0, seed=0,
+             transposed=False, h_weight=None, y_weight=None, row_lo=0):
+    """Elementwise bound on the difference of the next iterate of two faithful implementations
+    (each rounds an fp32-accurate value to the nearest bf16) whose inputs differ by at most
+    E_prev (the gathered operand) and E_h (the added one): rho + spacing_bf16(|t| + rho) with
+    rho = s |A| E_prev + a E_h + delta, since |RNE(x) - RNE(y)| <= |x - y| + one spacing.  t and
+    delta are ``step_exact`` on one implementation's inputs; delta's headroom over the standard
+    bound covers the other's slightly different S (E_prev is a few bf16 spacings)."""
+    indptr, indices, w, s, a = _step_operator(indptr, indices, w32, alpha, k, p_drop, seed,
+                                              transposed, h_weight, y_weight, row_lo)
+    E_prev = np.asarray(E_prev, dtype=np.float64)
+    W = sp.csr_matrix((np.abs(w), indices, indptr), shape=(indptr.size - 1, E_prev.shape[0]))
+    rho = s * (W @ E_prev) + delta
+    if E_h is not None:
+        rho = rho + abs(a) * np.asarray(E_h, dtype=np.float64)
+    return rho + spacing_bf16(np.abs(t) + rho)

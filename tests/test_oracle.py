@@ -146,6 +146,150 @@ def test_synth_graph_properties():
     assert a.has_sorted_indices
 
 
+# ---------------------------------------------------------------------------------------
+# bf16 storage reference (round_bf16 / spacing_bf16 / step_exact / close_bf16_step / envelope)
+# ---------------------------------------------------------------------------------------
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+
+
+def test_round_bf16_is_torch_bfloat16_bit_for_bit():
+    rng = np.random.default_rng(0)
+    rand = (rng.standard_normal(200_000) * np.exp(rng.uniform(-40, 40, 200_000))).astype(np.float32)
+    # exact ties: bf16 values (even and odd last bit) plus half a spacing; values that round up
+    # into the next binade (mantissa all ones); +-0, +-inf, the largest finite values, denormals
+    base = _bits(rng.standard_normal(4096).astype(np.float32)) & np.uint32(0xFFFF0000)
+    ties = (base | np.uint32(0x8000)).view(np.float32)
+    below = (base | np.uint32(0x7FFF)).view(np.float32)
+    above = (base | np.uint32(0x8001)).view(np.float32)
+    carry = np.array([0x3FFFFFFF, 0x3FFF8000, 0x3FFF7FFF, 0xBFFF8000, 0x7F7FFFFF, 0x7F7F8000,
+                      0x7F7F7FFF, 0xFF7F8000, 0x00000001, 0x00008000, 0x00018000, 0x007FFFFF,
+                      0x00000000, 0x80000000, 0x7F800000, 0xFF800000], dtype=np.uint32)
+    x = np.concatenate([rand, ties, below, above, carry.view(np.float32)])
+    got = O.round_bf16(x)
+    ref = torch.from_numpy(x).bfloat16().float().numpy()
+    assert np.array_equal(_bits(got), _bits(ref))
+    assert (_bits(got) & np.uint32(0xFFFF) == 0).all()
+    # NaN stays NaN (quiet and signalling, either sign), as in torch
+    nans = np.array([0x7FC00000, 0x7F800001, 0xFFC12345, 0x7FFFFFFF, 0x7F80FFFF], dtype=np.uint32)
+    out = O.round_bf16(nans.view(np.float32))
+    assert np.isnan(out).all() and (_bits(out) & np.uint32(0xFFFF) == 0).all()
+    assert torch.from_numpy(nans.view(np.float32).copy()).bfloat16().float().isnan().all()
+    assert O.round_bf16(np.ones((3, 5), np.float32)).shape == (3, 5)
+
+
+def test_spacing_bf16():
+    x = np.array([1.0, 1.99, 2.0, 0.75, -3.0, 0.0, 1e-45, 2.0 ** -126, 255.0, 256.0])
+    ref = np.array([2.0 ** -7, 2.0 ** -7, 2.0 ** -6, 2.0 ** -8, 2.0 ** -6, 2.0 ** -133,
+                    2.0 ** -133, 2.0 ** -133, 1.0, 2.0])
+    assert np.array_equal(O.spacing_bf16(x), ref)
+    # it is the gap between neighbouring bf16 values
+    v = O.round_bf16(np.random.default_rng(1).standard_normal(1000).astype(np.float32))
+    up = ((_bits(v) + np.uint32(0x10000)).view(np.float32)).astype(np.float64)
+    assert np.array_equal(np.abs(up - v.astype(np.float64)), O.spacing_bf16(v))
+
+
+def _emulate_step_fp32(ah32, Z, H, alpha):
+    """One forward step in fp32, every row accumulated in REVERSED entry order with separate
+    multiply and add (a summation order no kernel here uses), the value before the store."""
+    n, F = H.shape
+    ip, ix, w = ah32.indptr, ah32.indices, ah32.data.astype(np.float32)
+    deg = np.diff(ip)
+    acc = np.zeros((n, F), dtype=np.float32)
+    for j in range(int(deg.max())):
+        rows = np.flatnonzero(deg > j)
+        e = ip[rows + 1] - 1 - j
+        acc[rows] = acc[rows] + (w[e][:, None] * Z[ix[e]]).astype(np.float32)
+    s = np.float32(1.0) - np.float32(alpha)
+    return (s * acc).astype(np.float32) + (np.float32(alpha) * H).astype(np.float32)
+
+
+def test_bf16_step_bound_accepts_rounding_and_rejects_truncation():
+    """The bound of close_bf16_step on an fp32 emulation of the kernel: stored with
+    round-to-nearest-even it holds for every element; stored truncated it fails for about half
+    of them (a truncated value is up to a whole spacing below, twice the bound)."""
+    n, F, alpha = 3000, 20, 0.1
+    adj = O.synth_graph(n, 15000, 3)
+    ah = O.calc_a_hat(adj, "sym")
+    ah32 = ah.astype(np.float32)
+    rng = np.random.default_rng(5)
+    Z = O.round_bf16(rng.standard_normal((n, F)).astype(np.float32))
+    H = O.round_bf16(rng.standard_normal((n, F)).astype(np.float32))
+    pre = _emulate_step_fp32(ah32, Z, H, alpha)
+    t, delta = O.step_exact(ah32.indptr, ah32.indices, ah32.data, Z, H, alpha, 0, 0.0, 0)
+    # t is the fp64 step on the fp32 operands
+    s = float(np.float32(1.0) - np.float32(alpha))
+    ref = (s * (ah32.astype(np.float64) @ Z.astype(np.float64))
+           + float(np.float32(alpha)) * H.astype(np.float64))
+    assert np.abs(t - ref).max() <= 1e-15 and (delta > 0).all() and delta.max() < 1e-4
+    worst, share = O.close_bf16_step(O.round_bf16(pre), t, delta, "RNE")
+    assert worst <= 1.0 and share > 0.999
+    trunc = (_bits(pre) & np.uint32(0xFFFF0000)).view(np.float32)
+    with pytest.raises(AssertionError):
+        O.close_bf16_step(trunc, t, delta, "truncated")
+    bound = 0.5 * O.spacing_bf16(np.abs(t) + delta) + delta
+    ratio = np.abs(trunc.astype(np.float64) - t) / bound
+    assert (ratio > 1.0).mean() > 0.4 and 1.9 < ratio.max() <= 2.0 + 1e-3
+    assert (trunc == O.round_bf16(t.astype(np.float32))).mean() < 0.55
+    # a wrong value in one small element fails it too
+    bad = O.round_bf16(pre).copy()
+    i = np.unravel_index(np.argmin(np.abs(t)), t.shape)
+    bad[i] += np.float32(2.0 ** -6)
+    with pytest.raises(AssertionError):
+        O.close_bf16_step(bad, t, delta, "one element off")
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+def test_step_exact_dropout_matches_masked_operator(transposed):
+    """step_exact under dropout is the oracle's masked operator on the fp32 weights (mask, key
+    order, fp32 scale), also for a row range keyed on global rows and for the adjoint's keys."""
+    n, F, alpha, p, k, seed = 700, 5, 0.2, 0.3, 3, 11
+    ah32 = O.calc_a_hat(O.synth_graph(n, 3000, 4), "rw").astype(np.float32)
+    rng = np.random.default_rng(2)
+    Z, H = rng.standard_normal((n, F)), rng.standard_normal((n, F))
+    M = O.masked_operator(ah32.astype(np.float64), k, p, seed)  # forward keys (row, col)
+    op = ah32.T.tocsr() if transposed else ah32
+    op.sort_indices()
+    Mop = M.T.tocsr() if transposed else M
+    s, a = float(np.float32(1) - np.float32(alpha)), float(np.float32(alpha))
+    t, delta = O.step_exact(op.indptr, op.indices, op.data, Z, H, alpha, k, p, seed,
+                            transposed=transposed)
+    ref = s * (Mop @ Z) + a * H
+    # the fp32 product w32 * scale against the oracle's fp64 one: 2^-24 relative per weight
+    assert np.abs(t - ref).max() <= 2.0 ** -23 * (s * (abs(Mop) @ np.abs(Z))).max()
+    lo, hi = 200, 450
+    sub = op[lo:hi]
+    t2, d2 = O.step_exact(sub.indptr, sub.indices, sub.data, Z, H[lo:hi], alpha, k, p, seed,
+                          transposed=transposed, row_lo=lo)
+    assert np.array_equal(t2, t[lo:hi]) and np.array_equal(d2, delta[lo:hi])
+    t3, _ = O.step_exact(op.indptr, op.indices, op.data, Z, H, alpha, k, p, seed,
+                         transposed=transposed, h_weight=1.0, y_weight=alpha)
+    np.testing.assert_allclose(t3, a * s * (Mop @ Z) + H, rtol=0, atol=1e-6)
+    t4, _ = O.step_exact(op.indptr, op.indices, op.data, Z, None, alpha, k, p, seed,
+                         transposed=transposed)
+    np.testing.assert_allclose(t4, s * (Mop @ Z), rtol=0, atol=1e-6)
+
+
+def test_envelope_bounds_two_faithful_chains():
+    """Two fp32 emulations with different summation orders, both storing RNE bf16, iterated three
+    steps from the same H: they stay within the envelope, which stays a few spacings wide."""
+    n, F, alpha = 1500, 6, 0.1
+    ah32 = O.calc_a_hat(O.synth_graph(n, 7000, 9), "sym").astype(np.float32)
+    csr = (ah32.indptr, ah32.indices, ah32.data)
+    H = O.round_bf16(np.random.default_rng(3).standard_normal((n, F)).astype(np.float32))
+    za = zb = H
+    E = np.zeros((n, F))
+    for k in range(3):
+        t, delta = O.step_exact(*csr, za, H, alpha, k, 0.0, 0)
+        E = O.envelope(*csr, E, None, t, delta, alpha)
+        za = O.round_bf16(t.astype(np.float32))  # forward order, one rounding
+        zb = O.round_bf16(_emulate_step_fp32(ah32, zb, H, alpha))
+        assert (np.abs(za.astype(np.float64) - zb) <= E).all()
+        assert E.max() <= (k + 2) * 2.0 * O.spacing_bf16(np.abs(t).max())
+
+
 def test_drop_threshold_follows_the_float_abi():
     """p crosses the C ABI as a float: the oracle's threshold is float32(p) * 2^24 (0.3 ->
     5033165, one more than the double 0.3 gives), matching set_drop in appnp_capi.hip."""
