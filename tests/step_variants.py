@@ -8,6 +8,11 @@ every leading dimension is a multiple of V, and launch_step keeps that V.  ``exp
 mirrors those decisions on the host; ``CASES`` names, per cell (dtype, V, F mod V), a graph, a
 width and a layout that lands in it.  profiles/step_variants_hit.txt records the instantiations
 a kernel trace of the GPU modules saw, checked once against ``expected_kernel`` over CASES.
+
+``expected_grid`` mirrors the grid of launch_step (the block cap, the heavy blocks of a narrow
+launch), and the OVERRIDE_* tables name the cases that tests/override_worker.py runs under the
+tuning overrides (tests/test_gpu_overrides.py; their reach is proved on the host in
+tests/test_step_variants.py, their kernels and grids traced in profiles/override_paths_hit.txt).
 """
 
 import functools
@@ -27,6 +32,9 @@ K_HEAVY_ROW = 32     # kHeavyRow: a longer row gets a wavefront inside the narro
 K_HUB_ROW = 512      # kHubRow: a longer row is dispatched first by the wide launch
 K_WIDE_AVG_ROW = 24  # kWideAvgRow
 K_LATENCY_ROWS = 1 << 16
+K_WAVES_PER_BLOCK = 4   # kBlock / kWave
+K_MAX_BLOCKS = 1 << 22  # launch_step's cap on gridDim.x (APPNP_MAX_BLOCKS lowers it)
+K_HEAVY_BLOCKS = 4096   # most heavy-row blocks a narrow launch appends
 
 
 def line_ld(f, dtype):
@@ -93,20 +101,58 @@ def runs_wave_row(variant, n_heavy):
 EPI = {"FWD": 0, "BWD": 1, "PARTIAL": 2, "FINISH": 3, "ACCUM": 4, "CHEB": 5}
 
 
-def expected_kernel(dtype, epi, variant, nnz, nnz_rows, n_rows, n_heavy):
+def expected_kernel(dtype, epi, variant, nnz, nnz_rows, n_rows, n_heavy, uw=None, un=None):
     """The instantiation's name as a kernel trace prints it, k_step_wide / k_step_narrow
-    <T, V, G, EPI, U, TAIL>: U mirrors ``uw`` / ``un`` of launch_step and launch_g."""
+    <T, V, G, EPI, U, TAIL>: U mirrors ``uw`` / ``un`` of launch_step and launch_g.  ``uw`` /
+    ``un``: the APPNP_UW / APPNP_UN overrides (launch_g runs U = 1 for a uw that is none of 2, 4,
+    8, and the narrow U = 8 only at V <= 2)."""
     V, G, wide, rem, regime = variant
     latency = regime == "latency"
     long_rows = nnz >= K_WIDE_AVG_ROW * n_rows
     long_whole = (nnz_rows or nnz) >= K_WIDE_AVG_ROW * n_rows
     if wide:
-        U = 8 if (latency and n_heavy > 0) else 2 if (not latency and (long_rows or long_whole)) else 1
+        if uw is None:
+            uw = (8 if (latency and n_heavy > 0)
+                  else 2 if (not latency and (long_rows or long_whole)) else 1)
+        U = uw if uw in (2, 4, 8) else 1
     else:
-        U = 8 if (latency and V <= 2) else 4
+        if un is None:
+            un = 8 if latency else 4
+        U = 8 if (un == 8 and V <= 2) else 4
     T = "float" if dtype == "fp32" else "unsigned short"
     return (f"k_step_{'wide' if wide else 'narrow'}<{T}, {V}, {G}, {EPI[epi]}, {U}, "
             f"{'true' if rem else 'false'}>")
+
+
+def rows_per_block(variant):
+    """Rows a block of the launch takes per trip of its grid-stride loop: a wave per row (wide),
+    or 64 / G rows per wave (narrow)."""
+    _, G, wide, _, _ = variant
+    return K_WAVES_PER_BLOCK if wide else K_WAVES_PER_BLOCK * (K_WAVE // G)
+
+
+def slabs_of(variant, f):
+    V, G = variant[0], variant[1]
+    return (f + G * V - 1) // (G * V)
+
+
+def uncapped_blocks(variant, n_rows, n_hub):
+    """gridDim.x of the row pass before the cap: the hub rows count as virtual rows of a wide
+    launch only."""
+    rpb = rows_per_block(variant)
+    return (n_rows + (n_hub if variant[2] else 0) + rpb - 1) // rpb
+
+
+def expected_grid(variant, n_rows, n_hub, n_heavy, max_blocks=K_MAX_BLOCKS, *, f):
+    """(light_blocks, heavy_blocks, slabs) of launch_step's grid for ``f`` features: gridDim.x =
+    light_blocks + heavy_blocks, gridDim.y = slabs.  The hub list is dropped unless the launch
+    is wide, the heavy list unless it is narrow; the cap binds the row pass only."""
+    wide = variant[2]
+    light = min(uncapped_blocks(variant, n_rows, n_hub), min(max_blocks, K_MAX_BLOCKS))
+    heavy = 0
+    if not wide and n_heavy > 0:
+        heavy = min((n_heavy + K_WAVES_PER_BLOCK - 1) // K_WAVES_PER_BLOCK, K_HEAVY_BLOCKS)
+    return light, heavy, slabs_of(variant, f)
 
 
 # ---------------------------------------------------------------------------------------
@@ -114,6 +160,7 @@ def expected_kernel(dtype, epi, variant, nnz, nnz_rows, n_rows, n_heavy):
 # ---------------------------------------------------------------------------------------
 
 N_BIG = 66_000
+BH_N, BH_HEAVY, BH_FAN, BH_MUL = 100_000, 17_000, 33, 7919
 ROWS_N, ROWS_LO, ROWS_HI = 2000, 300, 1500   # the row-range graph R holds rows [300, 1500)
 ROWS_SHARDS, ROWS_SHARD_ROWS = 3, 700        # its source shards: columns [0, 700), .. [1400, 2000)
 
@@ -133,7 +180,12 @@ def adjacency(name):
     """L1: latency regime with heavy and hub rows.  Bs / Bsh / Bl: bandwidth regime with short
     rows, short rows plus heavy and hub rows, long rows.  R: the graph whose rows [300, 1500) a
     row-partitioned rank holds; its last held row reaches the last row of Zin and a row below
-    the range.  Md: MS-Academic-sized.  D: directed (upper triangle)."""
+    the range.  Md: MS-Academic-sized.  D: directed (upper triangle).  Dh: directed, bandwidth
+    regime: the upper triangle of Bs plus edges INTO six nodes (40 .. 600 each), so A_hat^T, which
+    the adjoint multiplies, has six heavy rows and a hub row (12 345) while A_hat has neither.  Bh: 17 000 heavy rows of
+    34 entries (more than the 16 384 waves of a narrow launch's heavy blocks) among short ones;
+    no RNG: node h < 17 000 is joined to 17 000 + ((33 h + t) 7919 mod 83 000), t = 0..32, and
+    7919 is coprime to 83 000, so the 561 000 edges are distinct and spread evenly."""
     if name == "L1":
         from test_gpu_parity import _hub_graph
 
@@ -154,6 +206,28 @@ def adjacency(name):
                            [ROWS_N - 1, 5])
     if name == "Md":
         return O.synth_graph(18333, 81894, 3)
+    if name == "Bh":
+        rest = BH_N - BH_HEAVY
+        h = np.repeat(np.arange(BH_HEAVY, dtype=np.int64), BH_FAN)
+        t = np.tile(np.arange(BH_FAN, dtype=np.int64), BH_HEAVY)
+        dst = BH_HEAVY + ((BH_FAN * h + t) * BH_MUL) % rest
+        half = sp.coo_matrix((np.ones(h.size, np.float32), (h, dst)), shape=(BH_N, BH_N)).tocsr()
+        a = (half + half.T).tocsr().astype(np.float32)
+        a.sort_indices()
+        return a
+    if name == "Dh":
+        rng = np.random.default_rng(37)
+        into = [7, 4099, 30_000, 47_111, N_BIG - 1, 12_345]
+        counts = [40, 45, 50, 55, 60, 600]
+        src = np.concatenate([rng.choice(N_BIG, c, replace=False) for c in counts])
+        dst = np.repeat(into, counts)
+        extra = sp.coo_matrix((np.ones(len(src), np.float32), (src, dst)),
+                              shape=(N_BIG, N_BIG)).tocsr()
+        a = ((sp.triu(adjacency("Bs"), format="csr") + extra) > 0).astype(np.float32).tocsr()
+        a.setdiag(0)
+        a.eliminate_zeros()
+        a.sort_indices()
+        return a
     if name == "D":
         a = sp.triu(O.synth_graph(1200, 5000, 3), format="csr").astype(np.float32)
         a.sort_indices()
@@ -426,3 +500,163 @@ def propagate_backward_views(G, dZ, dH, K, alpha, p_drop=0.0, seed=0):
                                      _vp(ws), ws_bytes, _stream(G.device))
     _lib.check("appnp_propagate_bwd", rc)
     return dH
+
+
+# ---------------------------------------------------------------------------------------
+# the cases of tests/override_worker.py (tests/test_gpu_overrides.py runs them)
+# ---------------------------------------------------------------------------------------
+
+# op: "fwd" (propagate_forward) / "bwd" (appnp_propagate_bwd on the views as given); ld None:
+# contiguous; mode / transpose: how the device graph is built
+OCase = namedtuple("OCase", "graph dtype f ld op K p_drop mode transpose",
+                   defaults=("fwd", 2, 0.0, "sym", False))
+# appnp_spmm on the 900 x 700 CSR of tests/test_gpu_parity.py::test_spmm_matches_dense
+SpmmCase = namedtuple("SpmmCase", "f p_drop transposed_key", defaults=(0.0, False))
+
+O_ALPHA, O_SEED = 0.1, 41
+DIRECTED = ("D", "Dh")
+SPMM_ROWS, SPMM_COLS, SPMM_DENSITY = 900, 700, 0.02
+
+# grid-stride loops: APPNP_MAX_BLOCKS = 1 and 7 (K = 2)
+OVERRIDE_CAPPED = [
+    OCase("L1", "fp32", 100, 104), OCase("L1", "fp32", 100, 104, "bwd"),
+    OCase("L1", "fp32", 7, 10), OCase("L1", "bf16", 13, 20, p_drop=0.3),
+    OCase("Bsh", "fp32", 7, 10), OCase("Bsh", "fp32", 7, 10, "bwd"),
+    OCase("Bsh", "bf16", 13, 20), OCase("Bsh", "fp32", 66, 68),
+    # the adjoint accumulates into dH, so a hub row computed twice shows in the value -- when the
+    # two computations fall into different trips: Bsh's hub row is row 12 345 (L1's is row 0,
+    # whose regular-pass turn comes in the same trip as its hub-first turn)
+    OCase("Bsh", "fp32", 66, 68, "bwd"),
+    OCase("Bs", "fp32", 13, 16),
+    OCase("D", "fp32", 16, None, mode="rw", transpose=True),
+    OCase("D", "fp32", 16, None, "bwd", mode="rw", transpose=True),
+    # D has no heavy and no hub row, in A_hat or in A_hat^T: it is the no-list case of the
+    # transposed CSR.  Dh's adjoint runs on an A_hat^T with six heavy rows and a hub row: the
+    # narrow launch appends heavy blocks for t_heavy, the wide one dispatches t_hub first
+    OCase("Dh", "fp32", 7, 10, "bwd", mode="rw", transpose=True),
+    OCase("Dh", "fp32", 66, 68, "bwd", mode="rw", transpose=True),
+    SpmmCase(130), SpmmCase(7), SpmmCase(130, 0.5, True),
+]
+# more heavy rows than the heavy blocks have waves: no override needed (and with the cap of 7,
+# both loops of the narrow kernel iterate in one launch)
+OVERRIDE_BH = [OCase("Bh", "fp32", 7, 8), OCase("Bh", "fp32", 7, 8, "bwd"),
+               OCase("Bh", "bf16", 13, 16)]
+# entries in flight and cache policy: APPNP_UW = 4, APPNP_UN = 4, APPNP_NT = 7.  The last case
+# is the narrow launch of the latency regime, the only one whose U (8) APPNP_UN = 4 changes.
+OVERRIDE_UNROLL = [
+    OCase("L1", "fp32", 100, 104, K=3), OCase("L1", "bf16", 100, 104, K=3),
+    OCase("L1", "fp32", 100, 104, "bwd"), OCase("L1", "bf16", 100, 104, "bwd"),
+    OCase("Bl", "fp32", 13, 16, K=3), OCase("Bs", "fp32", 13, 16, K=3),
+    OCase("Bs", "bf16", 9, 16, K=3), OCase("Md", "bf16", 15, None, K=3),
+    OCase("Md", "fp32", 7, None, K=3),
+]
+
+OVERRIDE_SETS = {"capped": OVERRIDE_CAPPED, "capped-bh": OVERRIDE_CAPPED + OVERRIDE_BH,
+                 "bh": OVERRIDE_BH, "unroll": OVERRIDE_UNROLL}
+
+
+def ocase_id(c):
+    if isinstance(c, SpmmCase):
+        return f"spmm-F{c.f}" + ("-drop" if c.p_drop else "") + ("-tkey" if c.transposed_key else "")
+    return (f"{c.graph}-{c.mode}-{c.dtype}-F{c.f}-ld{c.ld or c.f}-{c.op}-K{c.K}"
+            + ("-drop" if c.p_drop else ""))
+
+
+def ocase_seed(c):
+    if isinstance(c, SpmmCase):
+        return c.f * 131 + (5 if c.p_drop else 0)
+    return c.f * 131 + (c.ld or c.f) + (7 if c.op == "bwd" else 0)
+
+
+def spmm_matrix():
+    from test_gpu_parity import _rand_csr
+
+    return _rand_csr(SPMM_ROWS, SPMM_COLS, SPMM_DENSITY, 130)
+
+
+@functools.lru_cache(maxsize=None)
+def ostats(graph, mode="sym", transposed=False):
+    """``stats`` for any normalisation, and of A_hat^T (the CSR an adjoint multiplies when A_hat
+    is not symmetric)."""
+    ah = a_hat(graph, mode)
+    if transposed:
+        ah = ah.T.tocsr()
+    lens = np.diff(ah.indptr)
+    n = ah.shape[0]
+    return Stats(n, n, int(ah.nnz), int((lens > K_HEAVY_ROW).sum()), int((lens > K_HUB_ROW).sum()))
+
+
+def ocase_launch(c):
+    """(epi, lds, Stats, nnz known to the host) of the step launches of an override case."""
+    if isinstance(c, SpmmCase):  # appnp_spmm: no row lists, nnz unknown (-1) on the host
+        st = Stats(SPMM_COLS, SPMM_ROWS, -1, 0, 0)
+        return "PARTIAL", (c.f, c.f), st
+    ld = c.ld or c.f
+    self_adjoint = c.mode == "sym" and c.graph not in DIRECTED
+    st = ostats(c.graph, c.mode, c.op == "bwd" and not self_adjoint)
+    return ("FWD" if c.op == "fwd" else "BWD"), (ld, ld, line_ld(c.f, c.dtype)), st
+
+
+def ocase_variant(c):
+    epi, lds, st = ocase_launch(c)
+    dtype = "fp32" if isinstance(c, SpmmCase) else c.dtype
+    return expected_variant(dtype, c.f, lds, st.rows, st.nnz, st.n_heavy, st.n_hub)
+
+
+def ocase_prediction(c, max_blocks=K_MAX_BLOCKS, uw=None, un=None):
+    """(kernel name, (gridDim.x, gridDim.y)) of every step launch of the case."""
+    epi, lds, st = ocase_launch(c)
+    dtype = "fp32" if isinstance(c, SpmmCase) else c.dtype
+    v = ocase_variant(c)
+    light, heavy, slabs = expected_grid(v, st.rows, st.n_hub, st.n_heavy, max_blocks, f=c.f)
+    return (expected_kernel(dtype, epi, v, st.nnz, 0, st.rows, st.n_heavy, uw, un),
+            (light + heavy, slabs))
+
+
+# the remainder pass with many source blocks: APPNP_SB_ROWS = 1024 on a 66 000-node graph
+SB_N, SB_EDGES, SB_HUB, SB_ROWS, SB_NB = N_BIG, 4 * N_BIG, 3000, 1024, 65
+SbCase = namedtuple("SbCase", "width f op p_drop", defaults=("fwd", 0.0))
+SB_K = 3
+SB_CASES = [
+    SbCase(4, 100), SbCase(4, 36), SbCase(4, 33), SbCase(4, 3), SbCase(4, 36, p_drop=0.25),
+    SbCase(4, 100, "bwd"),
+    SbCase(8, 40), SbCase(8, 37), SbCase(8, 5), SbCase(8, 40, p_drop=0.25), SbCase(8, 40, "bwd"),
+    SbCase(16, 13), SbCase(16, 13, "bwd"),
+]
+# (name, weighted, mode per width): the unit graph stores no values in the copy; the weighted
+# one (values 0.5, 1, 2) keeps them, and its W8 copy is normalised 'rw' (no split adjoint there:
+# A_hat is not symmetric)
+SB_GRAPHS = [("unit", False, {4: "sym", 8: "sym", 16: "sym"}),
+             ("weighted", True, {4: "sym", 8: "rw", 16: "sym"})]
+SB_FEATURES = {4: 100, 8: 40, 16: 13}  # the width Graph.from_scipy lays the copy out for
+
+
+def sb_case_id(gname, c):
+    return f"{gname}-W{c.width}-F{c.f}-{c.op}" + ("-drop" if c.p_drop else "")
+
+
+def sb_cases_of(gname):
+    modes = dict((g[0], g[2]) for g in SB_GRAPHS)[gname]
+    return [c for c in SB_CASES if not (c.op == "bwd" and modes[c.width] != "sym")]
+
+
+@functools.lru_cache(maxsize=None)
+def sb_adjacency(weighted):
+    """O.synth_graph(66 000, 264 000) plus one hub row of 3000 entries, as the ``adj`` fixture of
+    tests/test_gpu_split.py builds it; ``weighted``: symmetric values drawn from 0.5, 1, 2."""
+    a = O.synth_graph(SB_N, SB_EDGES, seed=5).tolil()
+    rng = np.random.default_rng(6)
+    hub = rng.choice(np.arange(1, SB_N), size=SB_HUB, replace=False)
+    a[0, hub] = 1.0
+    a[hub, 0] = 1.0
+    a = sp.csr_matrix(a, dtype=np.float32)
+    if weighted:
+        up = sp.triu(a, k=1, format="csr").astype(np.float32)
+        up.data = np.random.default_rng(7).choice(np.float32([0.5, 1.0, 2.0]), size=up.nnz)
+        a = (up + up.T).tocsr().astype(np.float32)
+    a.sort_indices()
+    return a
+
+
+def pad4(f):
+    return (f + 3) // 4 * 4

@@ -724,7 +724,7 @@ def test_model_sparse_input_matches_dense(cora):
 
     pa = _lib()
     adj = adj_of(cora)
-    Xd = torch.from_numpy(cora["ppnp_X"])
+    Xd = torch.from_numpy(cora["ppnp_X"]).clone()  # not the session fixture's own array
     Xd[Xd < 0.9] = 0  # make it sparse
     Xs = SparseFeatures.from_scipy(sp.csr_matrix(Xd.numpy()), device=DEV)
     C = int(cora["n_classes"])
