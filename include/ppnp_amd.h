@@ -48,7 +48,8 @@ extern "C" {
  * _XCHG; appnp_tuning_overrides / appnp_tuning_names.
  * Added since, backward compatible (the version stays 2): the exact PPNP solver
  * appnp_solve_iterations, appnp_solve_weights, appnp_solve, appnp_solve_bwd and
- * appnp_plan_create_solve. */
+ * appnp_plan_create_solve; the column top-k selection appnp_topk_workspace_bytes and
+ * appnp_topk_columns. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -290,6 +291,37 @@ int appnp_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int6
 int appnp_solve_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, void* dH, int64_t ld_dh,
                     int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
                     void* stream);
+
+/*
+ * Sparse top-k PPR rows (batch-main.py:113-117, 134-152: the dense `ppr.topk` and the per-batch
+ * `model.ppr[idx_batch]` / `(ppr_sub > 0).any(dim=0)`): the k largest entries of every COLUMN of
+ * a row-major block, as the rows of a canonical CSR.
+ *   X: [n, b] fp32, leading dimension ld_x >= b -- the layout appnp_solve / appnp_propagate
+ *      write, Pi[:, idx] for b source nodes.
+ *   The candidate of (row r, column c) is v = (X[r, c] * rs) * cs in fp32, in that order, with
+ *   rs = row_scale[r] and cs = col_scale[c]; a NULL scale means no multiplication at all ('rw':
+ *   Pi[i, :] = D * Pi[:, i] / d_i with row_scale = D, col_scale = 1 / D[idx]).
+ *   Per column the k rows with the largest v are kept.  The order is total: equal values go by
+ *   the smaller row index, -0 equals +0, a NaN orders below every number (below -inf), and among
+ *   NaNs the lower index comes first.
+ *   out_idx[c * ld_out + j], out_val[c * ld_out + j], j < k: the kept rows of column c in
+ *   ASCENDING row index with their values v -- CSR row c of a b x n matrix with exactly k entries
+ *   per row, so its row pointer is k * arange(b + 1) and nothing has to be read back.  Elements
+ *   j >= k of an output row are not written (ld_out >= k).
+ *   ws: appnp_topk_workspace_bytes(n, b, k) bytes (monotone in n and b; 0 for an empty shape).
+ * The reference keeps every entry >= the k-th value (more than k on ties); this keeps exactly k.
+ * A chain of launches on `stream` (radix select, 8 bits per pass, on the order-preserving integer
+ * image of v; then count, scan and emit passes; X is read 6 times): stream-ordered, no allocation,
+ * no host synchronisation, graph-capturable, integer atomics only and therefore bitwise
+ * reproducible.  The per-launch timer records its launches as APPNP_KT_COPY.
+ * APPNP_EINVAL, before any device call: n < 0, b < 0, ld_x < b, k < 1, ld_out < k, n > INT32_MAX;
+ * then APPNP_OK when n * b == 0; then APPNP_EINVAL for k > n, a NULL X / out_idx / out_val / ws,
+ * or ws_bytes too small.  APPNP_ERANGE when n * b exceeds what one launch can cover (2^39).
+ */
+size_t appnp_topk_workspace_bytes(int64_t n, int64_t b, int k);
+int appnp_topk_columns(const float* X, int64_t ld_x, int64_t n, int64_t b, int k,
+                       const float* row_scale, const float* col_scale, int32_t* out_idx,
+                       float* out_val, int64_t ld_out, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]

@@ -9,7 +9,9 @@ from . import _lib
 from .graph import Graph
 from .model import APPNP, PPNP, CustomLinear
 from .ops import (SolvePlan, propagate, propagate_backward, propagate_forward, solve,
-                  solve_backward, solve_forward, solve_iterations, split_copy, step, step_split)
+                  solve_backward, solve_forward, solve_iterations, split_copy, step, step_split,
+                  topk_columns)
+from .ppr import SparsePPR, sparsified_ppr, topk_rows
 from .sparse import SparseFeatures, sparse_linear
 
 __all__ = [
@@ -30,5 +32,9 @@ __all__ = [
     "split_copy",
     "SparseFeatures",
     "sparse_linear",
+    "SparsePPR",
+    "topk_columns",
+    "topk_rows",
+    "sparsified_ppr",
     "_lib",
 ]

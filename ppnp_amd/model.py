@@ -20,6 +20,7 @@ from torch import nn
 
 from .graph import Graph
 from .ops import propagate, solve
+from .ppr import SparsePPR
 from .sparse import SparseFeatures, sparse_linear
 
 
@@ -75,8 +76,17 @@ def _encode(encoder, X, training):
     return encoder[4](encoder[3](encoder[2](h)))
 
 
+def _ppr_product(ppr, H):
+    """``ppr @ H`` (model.py:65); a SparsePPR takes the CSR product ``appnp_spmm``, whose
+    backward to H runs on the cached transpose (ppnp_amd/sparse.py)."""
+    if isinstance(ppr, SparsePPR):
+        return sparse_linear(ppr, H)
+    return ppr @ H
+
+
 class PPNP(nn.Module):
-    """model.py:41-67, unchanged semantics (dense ``ppr`` buffer)."""
+    """model.py:41-67, unchanged semantics (dense ``ppr`` buffer; ``ppr=`` may also be a
+    ``ppnp_amd.SparsePPR``)."""
 
     def __init__(self, n_features, n_classes, ppr, hidden_dim=64, drop_prob=0.5, bias=False):
         super().__init__()
@@ -91,7 +101,7 @@ class PPNP(nn.Module):
         if idx is not None:
             return self.ppr[idx] @ _encode(self.encoder, X, self.training)
         elif ppr is not None:
-            return ppr @ _encode(self.encoder, X, self.training)
+            return _ppr_product(ppr, _encode(self.encoder, X, self.training))
         else:
             raise Exception()
 
@@ -105,7 +115,8 @@ class APPNP(nn.Module):
     the device at the first forward on that device.
 
     forward(X, idx)      -> Z_K[idx]          (model.py:63 semantics, PPR truncated at K)
-    forward(X, ppr=P)    -> P @ encoder(X)    (model.py:65, batch mode, dense P unchanged)
+    forward(X, ppr=P)    -> P @ encoder(X)    (model.py:65, batch mode, dense P unchanged; a
+                                               SparsePPR P takes the CSR product)
     forward(X)           -> raises Exception() (model.py:66-67)
 
     ``edge_drop`` > 0 applies edge dropout inside the propagation kernel in training mode.
@@ -145,6 +156,7 @@ class APPNP(nn.Module):
         self.ppr_topk = None  # batch-main.py:113-117 sparsification of the lazy ``ppr``
         self._graph = None
         self._ppr = None  # (device, topk, dense Pi) built on first access of ``ppr``
+        self._sparse_ppr = None  # ((device, topk, tol), SparsePPR) of ``sparse_ppr``
         self._memo = None  # (key, Z_K) of the last no-grad eval-mode propagation
         self.memo_hits = 0
 
@@ -180,6 +192,21 @@ class APPNP(nn.Module):
                  else dense_ppr(g, K, self.alpha))
             self._ppr = (key, P)
         return self._ppr[1]
+
+    def sparse_ppr(self, topk: int, tol: float | None = None):
+        """The sparsified PPR matrix of batch-main.py:115-116 as an N x N ``SparsePPR``
+        (ppr.sparsified_ppr: top ``topk`` of every column, N * topk entries, no N x N matrix),
+        for ``P.batch(idx_batch)`` / ``P.rows(idx)`` and ``forward(X, ppr=...)``.  The columns
+        come from the same series as ``ppr`` or, with ``tol``, from the exact solver.  Cached
+        per (device, topk, tol)."""
+        from .ppr import sparsified_ppr
+
+        g = self.graph()
+        key = (g.device, int(topk), tol)
+        if self._sparse_ppr is None or self._sparse_ppr[0] != key:
+            K = int(math.ceil(math.log(self.PPR_TOL) / math.log(1.0 - self.alpha)))
+            self._sparse_ppr = (key, sparsified_ppr(g, int(topk), K, self.alpha, tol=tol))
+        return self._sparse_ppr[1]
 
     def get_norm(self):
         return sum((torch.sum(param ** 2) for param in self._reg_params))
@@ -226,6 +253,6 @@ class APPNP(nn.Module):
             self._memo = (key, Z) if key is not None else None
             return Z[idx]
         elif ppr is not None:
-            return ppr @ _encode(self.encoder, X, self.training)
+            return _ppr_product(ppr, _encode(self.encoder, X, self.training))
         else:
             raise Exception()

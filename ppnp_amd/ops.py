@@ -232,6 +232,46 @@ def solve(graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
     return torch.ops.ppnp_amd.solve(H, graph.key, m, float(alpha))
 
 
+# ---- sparse top-k PPR rows: the column selection (appnp_topk_columns) ----------------------
+
+
+def topk_columns(X: torch.Tensor, k: int, row_scale: torch.Tensor | None = None,
+                 col_scale: torch.Tensor | None = None):
+    """The k largest entries of every column of X [n, b] (fp32, unit column stride, a padded
+    leading dimension is passed through) via ``appnp_topk_columns``: ``(idx int32 [b, k],
+    val fp32 [b, k])``, each row sorted by ascending index -- the rows of a canonical CSR with
+    exactly k entries per row.  The candidate of (r, c) is ``(X[r, c] * row_scale[r]) *
+    col_scale[c]``; ties go to the smaller index, NaN orders last.  Stream-ordered on the current
+    stream, no host synchronisation, bitwise deterministic; see include/ppnp_amd.h."""
+    if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2:
+        raise TypeError("X must be a 2-D float32 tensor")
+    if not X.is_cuda:
+        raise ValueError("X must be a device tensor (there is no CPU fallback)")
+    n, b = int(X.shape[0]), int(X.shape[1])
+    if b > 0 and X.stride(1) != 1:
+        raise ValueError("X must have unit column stride")
+    k = int(k)
+    if k < 1 or (n * b > 0 and k > n):
+        raise ValueError(f"k must be in [1, {n}], got {k}")
+    scales = []
+    for name, t, m in (("row_scale", row_scale, n), ("col_scale", col_scale, b)):
+        if t is not None:
+            if t.dtype != torch.float32 or t.device != X.device or tuple(t.shape) != (m,):
+                raise ValueError(f"{name} must be float32 [{m}] on {X.device}")
+            t = t.contiguous()
+        scales.append(t)
+    idx = torch.empty(b, k, dtype=torch.int32, device=X.device)
+    val = torch.empty(b, k, dtype=torch.float32, device=X.device)
+    lib = _lib.load()
+    ws_bytes = int(lib.appnp_topk_workspace_bytes(n, b, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device) if ws_bytes else None
+    with torch.cuda.device(X.device):
+        rc = lib.appnp_topk_columns(_vp(X), _ld(X), n, b, k, _vp(scales[0]), _vp(scales[1]),
+                                    _vp(idx), _vp(val), k, _vp(ws), ws_bytes, _stream(X.device))
+    _lib.check("appnp_topk_columns", rc)
+    return idx, val
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:

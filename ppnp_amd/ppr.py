@@ -17,6 +17,11 @@ quirk (``ppr < thresh[:, -1]`` compares entry (i, j) with the threshold of row j
 COLUMN keeps its top k).  It needs every row's k-th largest value,
 i.e. all of Pi, which it streams in column chunks: O(N^2) work, small graphs only -- exactly
 the reference's own limit.
+
+``topk_rows`` / ``sparsified_ppr`` are the same protocol without the N x N matrix: PPR columns
+for a chunk of source nodes (``ppr_columns``), reduced on the device to each column's k largest
+entries by ``ops.topk_columns`` (``appnp_topk_columns``), kept as a device CSR (``SparsePPR``).
+``SparsePPR.batch`` is the minibatch wrapper batch-main.py:136-138 asks for.
 """
 
 from __future__ import annotations
@@ -24,7 +29,8 @@ from __future__ import annotations
 import torch
 
 from .graph import Graph
-from .ops import propagate_forward, solve_forward, solve_iterations
+from .ops import propagate_forward, solve_forward, solve_iterations, topk_columns
+from .sparse import SparseFeatures
 
 
 def _degrees(graph: Graph):
@@ -89,4 +95,124 @@ def batch_topk_quirk(graph: Graph, topk: int, K: int = 10, alpha: float = 0.1,
     P = dense_ppr(graph, K, alpha, chunk)
     thresh, _ = P.topk(topk, dim=-1)
     P[P < thresh[:, -1]] = 0
+    return P
+
+
+class SparsePPR(SparseFeatures):
+    """Rows of a (sparsified) PPR matrix as a device CSR, ``shape = (rows, N)``: the sparse
+    stand-in for the reference model's dense ``ppr`` buffer.  ``model(X, ppr=P)`` multiplies it
+    through ``sparse_linear`` (``appnp_spmm``; the backward runs on the cached transpose)."""
+
+    @classmethod
+    def from_dense(cls, P: torch.Tensor) -> "SparsePPR":
+        """The nonzero entries of a dense matrix, in canonical order."""
+        nz = P != 0
+        indptr = torch.zeros(P.shape[0] + 1, dtype=torch.int64, device=P.device)
+        indptr[1:] = nz.sum(dim=1).cumsum(0)
+        return cls(indptr, nz.nonzero()[:, 1], P[nz], P.shape, device=P.device)
+
+    def _take(self, idx: torch.Tensor):
+        """(entries per taken row, positions of their entries in ``indices`` / ``data``)."""
+        idx = torch.as_tensor(idx, device=self.device).long()
+        ip = self.indptr.long()
+        start = ip[idx]
+        lens = ip[idx + 1] - start
+        off = lens.cumsum(0) - lens
+        pos = torch.repeat_interleave(start - off, lens) + torch.arange(
+            int(lens.sum()), device=self.device)
+        return lens, pos
+
+    @staticmethod
+    def _indptr(lens: torch.Tensor) -> torch.Tensor:
+        ip = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=lens.device)
+        ip[1:] = lens.cumsum(0)
+        return ip
+
+    def rows(self, idx) -> "SparsePPR":
+        """The rows ``idx`` (in that order) over all N columns: ``ppr[idx]``."""
+        lens, pos = self._take(idx)
+        return SparsePPR(self._indptr(lens), self.indices[pos], self.data[pos],
+                         (lens.numel(), self.shape[1]), device=self.device)
+
+    def batch(self, idx):
+        """batch-main.py:140-142 on the sparse form: ``ppr_sub = ppr[idx]``,
+        ``sel = (ppr_sub > 0).any(dim=0)``, ``ppr_sub[:, sel]``.  Returns the
+        [len(idx) x |sel|] SparsePPR with its columns relabelled into ``sel``, and ``sel`` as the
+        sorted int64 column ids (index X with it: ``X[sel]``)."""
+        lens, pos = self._take(idx)
+        cols, vals = self.indices[pos].long(), self.data[pos]
+        sel = torch.unique(cols[vals > 0])  # sorted
+        new = torch.searchsorted(sel, cols).clamp_(max=max(int(sel.numel()) - 1, 0))
+        keep = sel[new] == cols if sel.numel() else torch.zeros_like(cols, dtype=torch.bool)
+        if not bool(keep.all()):  # a stored entry <= 0 in a column that no row selects
+            row = torch.repeat_interleave(torch.arange(lens.numel(), device=self.device), lens)
+            lens = torch.bincount(row[keep], minlength=lens.numel())
+            new, vals = new[keep], vals[keep]
+        sub = SparsePPR(self._indptr(lens), new, vals, (lens.numel(), int(sel.numel())),
+                        device=self.device)
+        return sub, sel
+
+
+def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
+              tol: float | None = None, chunk: int = 128) -> SparsePPR:
+    """Pi[idx, :] reduced to each row's k largest entries, as a SparsePPR [len(idx) x N] with
+    exactly k entries per row (ties at the k-th value go to the smaller column).  The sources
+    are taken ``chunk`` at a time: their PPR columns (``ppr_columns``: the K-step series, or
+    with ``tol`` the solver's columns) are selected on the device by ``ops.topk_columns``, with
+    no transposed copy and no read-back.  sym: the rows are the columns; rw:
+    Pi[i, :] = D * Pi[:, i] / d_i, applied as the kernel's row and column scales.  Memory is
+    one N x chunk block plus the len(idx) * k result.  Undirected graphs only."""
+    if not graph.symmetric:
+        raise ValueError("topk_rows needs an undirected graph (symmetric A)")
+    idx = torch.as_tensor(idx, device=graph.device).long()
+    rs = cs_all = None
+    if graph.mode != "sym":
+        _, _, _, dinv = graph.csr()  # fp64 1 / D
+        rs = (1.0 / dinv).float()
+        cs_all = dinv[idx].float()
+    ix, dv = [], []
+    for s in range(0, int(idx.numel()), int(chunk)):
+        part = idx[s:s + chunk]
+        cols = ppr_columns(graph, part, K, alpha, tol)
+        i, v = topk_columns(cols, k, rs, None if cs_all is None else cs_all[s:s + chunk])
+        ix.append(i.reshape(-1))
+        dv.append(v.reshape(-1))
+    B = int(idx.numel())
+    indptr = torch.arange(B + 1, dtype=torch.int64, device=graph.device) * int(k)
+    empty_i = torch.empty(0, dtype=torch.int32, device=graph.device)
+    return SparsePPR(indptr, torch.cat(ix) if ix else empty_i,
+                     torch.cat(dv) if dv else empty_i.float(), (B, graph.n), device=graph.device)
+
+
+def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
+                   tol: float | None = None, chunk: int = 128) -> SparsePPR:
+    """The sparsified Pi of batch-main.py:115-116 as an N x N SparsePPR, without the N x N
+    matrix.  That line's broadcasting makes every COLUMN keep its top k,
+    so the k largest entries of every column Pi[:, j] are selected chunk by chunk
+    (``ppr_columns`` + ``ops.topk_columns``) as a CSC with exactly k entries per column, which
+    ``appnp_csr_transpose`` turns into the CSR.  Memory is N * k entries (twice: the CSC stays
+    as the cached transpose the backward needs) plus one N x chunk block; the N^2 guard of
+    ``dense_ppr`` does not apply.
+
+    One deviation from the reference: it keeps every entry >= the threshold -- more than k on
+    ties, and in practice sometimes fewer, because its fp64 inverse is not exactly symmetric and
+    column j is compared with the threshold of ROW j.  This function keeps exactly k per column,
+    by the kernel's tie rule (equal values: the smaller row index first).  For 'rw', where Pi is
+    not symmetric, this is the column-wise reading as well."""
+    if not graph.symmetric:
+        raise ValueError("sparsified_ppr needs an undirected graph (symmetric A)")
+    n = graph.n
+    if n * int(k) >= 2**31:
+        raise ValueError("sparsified_ppr: N * k exceeds the int32 CSR index range")
+    ix, dv = [], []
+    for s in range(0, n, int(chunk)):
+        part = torch.arange(s, min(n, s + chunk), device=graph.device)
+        i, v = topk_columns(ppr_columns(graph, part, K, alpha, tol), k)
+        ix.append(i.reshape(-1))
+        dv.append(v.reshape(-1))
+    indptr = torch.arange(n + 1, dtype=torch.int64, device=graph.device) * int(k)
+    csc = SparsePPR(indptr, torch.cat(ix), torch.cat(dv), (n, n), device=graph.device)
+    ip, jx, val = csc.transpose()
+    P = SparsePPR(ip, jx, val, (n, n), device=graph.device)
+    P._t = (csc.indptr, csc.indices, csc.data)  # the CSC is P^T: the backward's operand
     return P

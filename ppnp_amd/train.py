@@ -16,6 +16,10 @@ seeding and early stopping are host bookkeeping, restated so that the harness ru
 the reference; tests/test_train.py pins them to the reference's own outputs.
 
     python -m ppnp_amd.train --dataset cora_ml --n-runs 5      # data: tests/golden/*.npz
+
+With ``--batch-size B --ppr-topk k`` (``--model appnp``) it follows the reference's second entry
+point, batch-main.py:104-169, instead: minibatches of top-k-sparsified PPR rows, on the sparse
+matrix of ``APPNP.sparse_ppr`` (no N x N matrix; ppnp_amd/ppr.py).
 """
 
 from __future__ import annotations
@@ -146,7 +150,7 @@ def load_dataset(name):
 
 
 # -- main.py:71-165 -------------------------------------------------------------------------
-def run_once(adj, attr, labels, args, device):
+def run_once(adj, attr, labels, args, device, stats=None):
     from .model import APPNP, PPNP
 
     idx_split_args = {"ntrain_per_class": args.ntrain_per_class, "nstopping": args.nstopping,
@@ -177,6 +181,9 @@ def run_once(adj, attr, labels, args, device):
                       tol=getattr(args, "tol", 1e-6)).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     early_stopping = SimpleEarlyStopping(model)
+    if getattr(args, "batch_size", None):
+        return _run_batches(model, opt, early_stopping, X, (idx_train, idx_stop, idx_valid),
+                            (y_train, y_stop, y_valid), args, stats)
     t = time.time()
     for epoch in range(args.max_epochs):
         model.train()
@@ -198,6 +205,53 @@ def run_once(adj, attr, labels, args, device):
         record = {"epoch": int(epoch), "elapsed": float(time.time() - t),
                   "train_acc": float(train_acc), "stop_acc": float(stop_acc),
                   "valid_acc": float(valid_acc)}
+        if args.verbose:
+            print(json.dumps(record), file=sys.stderr)
+        if early_stopping.should_stop(acc=float(stop_acc), loss=float(stop_loss), epoch=epoch,
+                                      record=record):
+            break
+    return early_stopping.record
+
+
+def _run_batches(model, opt, early_stopping, X, idx, y, args, stats=None):
+    """batch-main.py:104-169: a shuffled loader over idx_train; per batch the sparsified PPR
+    rows of the batch, the union ``sel`` of their columns, ``X[sel]`` and
+    ``model(X_batch, ppr=ppr_sub)``; stopping and validation through the sparsified rows too,
+    as the reference evaluates on its sparsified buffer.  The records carry the reference's
+    keys; the one-time build of the sparse matrix goes to ``stats["ppr_build"]`` (seconds)."""
+    from torch.utils.data import DataLoader, TensorDataset
+
+    idx_train, idx_stop, idx_valid = idx
+    y_train, y_stop, y_valid = y
+    loader = DataLoader(TensorDataset(idx_train.cpu(), y_train.cpu()),
+                        batch_size=args.batch_size, shuffle=True, num_workers=0)
+    t0 = time.time()
+    P = model.sparse_ppr(args.ppr_topk, tol=args.tol if args.exact else None)
+    torch.cuda.synchronize()
+    if stats is not None:
+        stats["ppr_build"] = time.time() - t0
+    P_stop, P_valid = P.rows(idx_stop), P.rows(idx_valid)
+    t = time.time()
+    for epoch in range(args.max_epochs):
+        model.train()
+        for idx_batch, y_batch in loader:
+            ppr_sub, sel = P.batch(idx_batch.to(X.device))
+            logits = model(X[sel], idx=None, ppr=ppr_sub)
+            loss = F.cross_entropy(logits, y_batch.to(X.device))
+            loss = loss + args.reg_lambda / 2 * model.get_norm()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+
+        model.eval()
+        with torch.no_grad():
+            logits = model(X, ppr=P_stop)
+            stop_loss = F.cross_entropy(logits, y_stop)
+            stop_loss = stop_loss + args.reg_lambda / 2 * model.get_norm()
+            stop_acc = (logits.argmax(dim=-1) == y_stop).float().mean()
+            valid_acc = (model(X, ppr=P_valid).argmax(dim=-1) == y_valid).float().mean()
+        record = {"epoch": int(epoch), "elapsed": float(time.time() - t),
+                  "stop_acc": float(stop_acc), "valid_acc": float(valid_acc)}
         if args.verbose:
             print(json.dumps(record), file=sys.stderr)
         if early_stopping.should_stop(acc=float(stop_acc), loss=float(stop_loss), epoch=epoch,
@@ -240,9 +294,24 @@ def parse_args(argv=None):
     p.add_argument("--model", default="appnp", choices=["appnp", "ppnp"])
     p.add_argument("--sparse-x", action="store_true",
                    help="keep the attribute matrix as a CSR on the GPU (sparse encoder input)")
+    p.add_argument("--batch-size", type=int, default=None,
+                   help="--model appnp: minibatch training on sparsified PPR rows "
+                        "(batch-main.py); needs --ppr-topk")
+    p.add_argument("--ppr-topk", type=int, default=None,
+                   help="entries kept per column of the PPR matrix (batch-main.py:115-116)")
     p.add_argument("--test", action="store_true")
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
+    if args.batch_size is not None:
+        if args.batch_size < 1 or not args.ppr_topk or args.ppr_topk < 1:
+            p.error("--batch-size needs a positive value and a positive --ppr-topk")
+        if args.model != "appnp":
+            p.error("--batch-size needs --model appnp")
+        if args.sparse_x:
+            p.error("--batch-size cannot be combined with --sparse-x: a minibatch takes the "
+                    "rows X[sel], which needs a dense X")
+    elif args.ppr_topk is not None:
+        p.error("--ppr-topk needs --batch-size")
     if "ms_academic" in args.dataset:  # main.py:56-59
         args.alpha = 0.2
         args.nknown = 5000
@@ -254,9 +323,11 @@ def main(argv=None):
     set_seeds(args.seed)
     device = torch.device("cuda")
     adj, attr, labels = load_dataset(args.dataset)
-    records = []
+    records, builds = [], []
     for _ in range(args.n_runs):
-        rec = run_once(adj, attr, labels, args, device)
+        stats = {}
+        rec = run_once(adj, attr, labels, args, device, stats)
+        builds.append(stats.get("ppr_build", 0.0))
         print(rec, flush=True)
         records.append(rec)
     acc = np.array([r["valid_acc"] for r in records])
@@ -265,6 +336,10 @@ def main(argv=None):
                if len(acc) > 1 else 0.0,
                "epochs_mean": float(np.mean([r["epoch"] for r in records])),
                "elapsed_mean": float(np.mean([r["elapsed"] for r in records]))}
+    if args.batch_size:
+        summary.update({"batch_size": args.batch_size, "ppr_topk": args.ppr_topk,
+                        "ppr_build_mean": float(np.mean(builds)),
+                        "records": records})
     print(json.dumps(summary), flush=True)
     return summary
 
