@@ -49,7 +49,8 @@ extern "C" {
  * Added since, backward compatible (the version stays 2): the exact PPNP solver
  * appnp_solve_iterations, appnp_solve_weights, appnp_solve, appnp_solve_bwd and
  * appnp_plan_create_solve; the column top-k selection appnp_topk_workspace_bytes and
- * appnp_topk_columns. */
+ * appnp_topk_columns; PPR columns by forward push, appnp_push_workspace_bytes and
+ * appnp_push_columns, with the timer kind APPNP_KT_PUSH. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -324,6 +325,48 @@ int appnp_topk_columns(const float* X, int64_t ld_x, int64_t n, int64_t b, int k
                        float* out_val, int64_t ld_out, void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * PPR columns by local forward push (Andersen-Chung-Lang): X = Pi[:, sources], the block
+ * appnp_topk_columns reads, at a cost per source that follows its residual (about 1 / eps and the
+ * local neighbourhood) instead of n.  A third way to the columns, beside the K-step series
+ * (appnp_propagate) and the solver (appnp_solve) of one-hot columns.
+ *
+ * Per source s, with T = (1 - alpha) A_hat: an estimate p and a residual r, int64 fixed point in
+ * units of 2^-44; p = 0, r = e_s (2^44 at s).  A round is synchronous.  Its frontier is
+ * F = { j : r_j >= thr_j }, thr_j = max(1, ceil(eps w_j 2^44)) in fp64, w_j = 1 / dinv_j
+ * (= sqrt(d_j)) for 'sym' and 1 for 'rw'.  Every i in F is taken (t = r_i, r_i = 0) before
+ * anything is added; then p_i += (int64)((double)t * (double)alpha) and, for every entry (j, i)
+ * of column i of A_hat, r_j += (int64)(((double)t * (double)val) * (double)(1.0f - alpha)), both
+ * conversions truncating, alpha and val the fp32 values.  It stops when F is empty or after
+ * max_rounds rounds.  X[j, c] = (float)((double)p_j 2^-44).  All sums are integer sums and a
+ * round is a pure function of the state before it: the result is bitwise reproducible and does
+ * not depend on scheduling.  With F empty, |Pi[j, s] - X[j, c]| < eps w_j (eps sqrt(d_j) for sym,
+ * eps for rw).  A_hat >= 0 is assumed (unweighted graphs, non-negative weights): a graph that
+ * violates it can give wrong numbers, never an out-of-range access.
+ *
+ *   sources: b node indices (device memory); duplicates are independent columns; an index
+ *      outside [0, n) gives an all-zero column with left = -1.
+ *   X: [n, b] fp32, ld_x >= b; every element of X[:, :b] is written, padding columns are not.
+ *   rounds[c]: rounds run for column c; left[c]: frontier size at exit, 0 = the bound holds.
+ *      Each may be NULL.
+ *   ws: appnp_push_workspace_bytes(n, b) bytes (monotone in n and b; 0 for an empty shape), 16-byte
+ *      aligned: per source r, p and the takes of a round as int64 [n] and two frontier lists of
+ *      capacity n as int32, plus the n thresholds.  The call clears r and p on the stream itself.
+ * Column i of A_hat is row i of A_hat^T: 'sym' walks the stored CSR, 'rw' the transpose built with
+ * APPNP_GRAPH_TRANSPOSE.  One workgroup per source with the whole round loop inside one launch
+ * (timed as APPNP_KT_PUSH; the clear, the thresholds and the final p -> X launch as
+ * APPNP_KT_COPY): workgroup barriers only, no workgroup waits for another, 64-bit integer atomics
+ * only.  Stream-ordered, no allocation, no host synchronisation, graph-capturable.
+ * APPNP_EINVAL, before any device call: a NULL g, b < 0, ld_x < b, alpha outside (0, 1], eps
+ * outside (0, 1), max_rounds < 1; then APPNP_OK when b == 0 or n == 0; then APPNP_EINVAL for a
+ * NULL sources / X / ws or ws_bytes too small.  APPNP_ENOTSUP: a row-partitioned graph, a graph
+ * whose symmetric flag is 0 (as appnp_solve), 'rw' without the transpose.  fp32 only.
+ */
+size_t appnp_push_workspace_bytes(int64_t n, int64_t b);
+int appnp_push_columns(const appnp_graph* g, const int64_t* sources, int64_t b, float alpha,
+                       float eps, int max_rounds, float* X, int64_t ld_x, int32_t* rounds,
+                       int32_t* left, void* ws, size_t ws_bytes, void* stream);
+
+/*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]
  *                                                   + alpha H[i-row_lo],  i in [row_lo,row_hi)
  *   Zin: all n rows (global row index), Zout/H: the held rows only.
@@ -561,7 +604,8 @@ enum appnp_kernel_kind {
   APPNP_KT_REM = 3,    /* the persistent L2-blocked remainder pass                          */
   APPNP_KT_LOCAL = 4,  /* appnp_step(_split) PART_LOCAL: the local-column product           */
   APPNP_KT_REMOTE = 5, /* appnp_step(_split) PART_REMOTE: the remote columns + epilogue     */
-  APPNP_KT_XCHG = 6    /* appnp_dist_propagate: one call of the exchange (all-gather)       */
+  APPNP_KT_XCHG = 6,   /* appnp_dist_propagate: one call of the exchange (all-gather)       */
+  APPNP_KT_PUSH = 7    /* appnp_push_columns: the forward-push launch (all rounds)          */
 };
 int appnp_kernel_timer_begin(int max_launches, void* stream);
 int appnp_kernel_timer_end(float* ms, int* kinds, int max, int* n_out);

@@ -36,7 +36,8 @@ GRAPH_SB_W16 = 0x800  # up to 16
 F32, BF16 = 0, 1
 PART_ALL, PART_LOCAL, PART_REMOTE = 0, 1, 2
 SHARDS_FIRST, SHARDS_ACC, SHARDS_LAST, SHARDS_ONLY = 0, 1, 2, 3  # appnp_shard_mode
-KT_COPY, KT_STEP, KT_REM, KT_LOCAL, KT_REMOTE, KT_XCHG = 1, 2, 3, 4, 5, 6  # appnp_kernel_kind
+# appnp_kernel_kind
+KT_COPY, KT_STEP, KT_REM, KT_LOCAL, KT_REMOTE, KT_XCHG, KT_PUSH = 1, 2, 3, 4, 5, 6, 7
 
 _vp, _i64, _i32, _f32, _u64, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 
@@ -100,6 +101,11 @@ _SIGS = {
     "appnp_topk_columns": (
         _i32,
         [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp],
+    ),
+    "appnp_push_workspace_bytes": (_sz, [_i64, _i64]),
+    "appnp_push_columns": (
+        _i32,
+        [_vp, _vp, _i64, _f32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
     ),
     "appnp_plan_launch": (_i32, [_vp, _vp]),
     "appnp_plan_destroy": (None, [_vp]),

@@ -1,0 +1,268 @@
+// appnp_push.hip -- PPR columns by local forward push (Andersen-Chung-Lang), gfx950.
+//
+// appnp_push_columns writes X = Pi[:, sources] (n x b, the block appnp_topk_columns reads) like
+// appnp_solve does for one-hot columns, but a source's work follows its residual, not n: with
+// T = (1-alpha) A_hat it keeps an estimate p and a residual r (p = 0, r = e_s at the start) and
+// moves r_i to alpha r_i in p_i and T[:, i] r_i in r, for the nodes i whose residual has reached
+// the threshold eps * w_i only.  DESIGN.md 4.7.
+//
+// Fixed point.  p and r are int64 in units of 2^-44.  A round is synchronous: its frontier is
+// F = { j : r_j >= thr_j }, thr_j = max(1, ceil(eps w_j 2^44)) (w_j = 1 / dinv_j for sym, 1 for
+// rw); every i in F is TAKEN first (t_i = r_i, r_i = 0), then pushed:
+//   p_i += (int64)((double)t_i * alpha)
+//   r_j += (int64)(((double)t_i * val) * (1 - alpha))   for every entry (j, i) of column i
+// Every sum is an integer sum and a round is a pure function of the state before it, so X does
+// not depend on the schedule: it is bitwise reproducible (tests/push_ref.py replays it in numpy).
+//
+// Shape.  One workgroup of kPushBlock threads per source, the whole round loop inside the kernel,
+// workgroup barriers only: a workgroup touches nothing but its own source's slices of the
+// workspace, so no workgroup ever waits for (or reads from) another one.  Per round:
+//   take   a thread per frontier entry q: t = exchange(r_i, 0) into take[q]; p_i += alpha t
+//   push   a wave per frontier entry, lanes over the entries of row i of A_hat^T (coalesced col /
+//          val loads): old = fetch_add(r_j, c); the one add that carries r_j over thr_j appends j
+//          to the next frontier list (LDS counter; the store is clamped to the list's capacity).
+//          A frontier shorter than the workgroup's wave count is pushed by all waves together,
+//          each on every kPushWaves-th chunk of 64 entries of a row.
+// A_hat >= 0 is assumed: residuals then only grow between takes, so a node is appended once per
+// round.  r is accessed by 64-bit integer atomics only; the lists and takes are plain stores read
+// after a workgroup barrier.  The launches on `stream`: clear of r and p, thresholds (sym),
+// push, emit (p -> X through an LDS transpose, coalesced on both sides).
+#include <algorithm>
+
+#include "appnp_internal.h"
+#include "../../include/ppnp_amd.h"
+
+namespace appnp {
+namespace {
+
+constexpr int kPushBlock = 1024;
+constexpr int kPushWaves = kPushBlock / kWave;
+constexpr int64_t kOne = (int64_t)1 << 44;  // 1.0 in fixed point
+constexpr double kUnit = 1.0 / 17592186044416.0;  // 2^-44
+constexpr int kEmitTile = 32;
+
+struct PushArgs {
+  const int32_t* row_ptr;  // A_hat^T: row i holds the entries (j, i) of column i of A_hat
+  const int32_t* col;
+  const float* val;
+  const double* dinv;      // sym: w_j = 1 / dinv_j; null for rw (w_j = 1)
+  const int64_t* sources;
+  int64_t n, b;
+  float alpha, beta;       // beta = 1.0f - alpha, in fp32
+  float eps;
+  int max_rounds;
+  int64_t* thr;            // [n] (sym only)
+  int64_t* r;              // [b][n]
+  int64_t* p;              // [b][n]
+  int64_t* take;           // [b][n] the takes of a round, by frontier position
+  int32_t* lists;          // [b][2][n]
+  int32_t* rounds;
+  int32_t* left;
+  float* x;
+  int64_t ld_x;
+};
+
+__host__ __device__ __forceinline__ int64_t threshold(float eps, double w) {
+  const double t = ceil(((double)eps * w) * 17592186044416.0);
+  return t < 1.0 ? (int64_t)1 : (int64_t)t;
+}
+
+__global__ __launch_bounds__(kBlock) void k_push_thr(PushArgs a) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j < a.n) a.thr[j] = threshold(a.eps, 1.0 / a.dinv[j]);
+}
+
+// r and p of every source to zero: 16-byte stores, grid-stride
+__global__ __launch_bounds__(kBlock) void k_push_clear(ulonglong2* dst, int64_t n16) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n16; i += stride)
+    dst[i] = make_ulonglong2(0ull, 0ull);
+}
+
+__device__ __forceinline__ int64_t fetch_add(int64_t* p, int64_t v) {
+  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kPushBlock) void k_push(PushArgs a) {
+  __shared__ int cnt[2];
+  const int64_t c = blockIdx.x;
+  const int64_t n = a.n;
+  const int64_t s = a.sources[c];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  if (s < 0 || s >= n) {  // whole workgroup: the column stays zero
+    if (tid == 0) {
+      if (a.rounds) a.rounds[c] = 0;
+      if (a.left) a.left[c] = -1;
+    }
+    return;
+  }
+  int64_t* r = a.r + c * n;
+  int64_t* p = a.p + c * n;
+  int64_t* take = a.take + c * n;
+  int32_t* list = a.lists + 2 * c * n;
+  const int64_t thr_rw = threshold(a.eps, 1.0);
+  if (tid == 0) {
+    const int64_t thr_s = a.thr ? a.thr[s] : thr_rw;
+    __hip_atomic_store(r + s, kOne, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    list[0] = (int32_t)s;
+    cnt[0] = kOne >= thr_s ? 1 : 0;
+    cnt[1] = 0;
+  }
+  __syncthreads();
+  const double alpha = (double)a.alpha, beta = (double)a.beta;
+  int cur = 0, round = 0;
+  int64_t m = 0;  // frontier size
+  for (;;) {
+    m = std::min<int64_t>((int64_t)cnt[cur], n);  // an append past the capacity was not stored
+    if (m == 0 || round == a.max_rounds) break;
+    if (tid == 0) cnt[cur ^ 1] = 0;  // last read a round ago, two barriers back
+    int32_t* fl = list + (int64_t)cur * n;
+    int32_t* nl = list + (int64_t)(cur ^ 1) * n;
+    for (int64_t q = tid; q < m; q += kPushBlock) {
+      const int64_t i = fl[q];
+      const int64_t t =
+          __hip_atomic_exchange(r + i, (int64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      take[q] = t;
+      fetch_add(p + i, (int64_t)((double)t * alpha));
+    }
+    __syncthreads();  // every take before every add
+    // entries [off, off + kWave) of every `step` entries of the rows q0, q0 + dq, ...
+    const bool together = m < kPushWaves;
+    const int64_t q0 = together ? 0 : wave, dq = together ? 1 : kPushWaves;
+    const int off = (together ? wave * kWave : 0) + lane;
+    const int step = together ? kPushBlock : kWave;
+    for (int64_t q = q0; q < m; q += dq) {
+      const int64_t i = fl[q];
+      const double t = (double)take[q];
+      const int64_t e1 = a.row_ptr[i + 1];
+      for (int64_t e = (int64_t)a.row_ptr[i] + off; e < e1; e += step) {
+        const int64_t j = a.col[e];
+        const int64_t add = (int64_t)((t * (double)a.val[e]) * beta);
+        if (j < 0 || j >= n) continue;  // never with a graph this library built
+        const int64_t old = fetch_add(r + j, add);
+        const int64_t th = a.thr ? a.thr[j] : thr_rw;
+        if (old < th && old + add >= th) {
+          const int pos = atomicAdd(&cnt[cur ^ 1], 1);
+          if (pos < n) nl[pos] = (int32_t)j;
+        }
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+    ++round;
+  }
+  if (tid == 0) {
+    if (a.rounds) a.rounds[c] = round;
+    if (a.left) a.left[c] = (int32_t)m;
+  }
+}
+
+// X[j, c] = (float)(p[c][j] 2^-44): a 32 x 32 tile through LDS, reads along j, writes along c
+__global__ __launch_bounds__(kBlock) void k_push_emit(PushArgs a) {
+  __shared__ int64_t tile[kEmitTile][kEmitTile + 1];
+  const int64_t jt = (int64_t)blockIdx.x * kEmitTile, ct = (int64_t)blockIdx.y * kEmitTile;
+  const int lx = threadIdx.x & (kEmitTile - 1), ly = threadIdx.x / kEmitTile;
+  for (int y = ly; y < kEmitTile; y += kBlock / kEmitTile) {
+    const int64_t c = ct + y, j = jt + lx;
+    if (c < a.b && j < a.n) tile[y][lx] = a.p[c * a.n + j];
+  }
+  __syncthreads();
+  for (int y = ly; y < kEmitTile; y += kBlock / kEmitTile) {
+    const int64_t j = jt + y, c = ct + lx;
+    if (c < a.b && j < a.n) a.x[j * a.ld_x + c] = (float)((double)tile[lx][y] * kUnit);
+  }
+}
+
+inline size_t round_up(size_t x, size_t al) { return (x + al - 1) / al * al; }
+
+// bytes of the workspace parts: the thresholds, then per source r, p, the takes and two lists
+inline size_t thr_bytes(int64_t n) { return round_up((size_t)n * sizeof(int64_t), 256); }
+inline size_t slab_bytes(int64_t n, int64_t b) { return (size_t)n * (size_t)b * sizeof(int64_t); }
+
+inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
+
+template <typename Launch>
+inline int timed_launch(hipStream_t s, int kind, Launch launch) {
+  ktimer_begin(s);
+  launch();
+  const int rc = launch_err();
+  ktimer_mark(s, kind);
+  return rc;
+}
+
+}  // namespace
+}  // namespace appnp
+
+extern "C" size_t appnp_push_workspace_bytes(int64_t n, int64_t b) {
+  using namespace appnp;
+  if (n <= 0 || b <= 0 || n > INT32_MAX) return 0;
+  // r, p, take as int64 [b][n]; two int32 lists of capacity n per source: one more such slab
+  return round_up(thr_bytes(n) + 4 * slab_bytes(n, b), 256);
+}
+
+extern "C" int appnp_push_columns(const appnp_graph* g, const int64_t* sources, int64_t b,
+                                  float alpha, float eps, int max_rounds, float* X, int64_t ld_x,
+                                  int32_t* rounds, int32_t* left, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  using namespace appnp;
+  if (!g || b < 0 || ld_x < b || max_rounds < 1) return APPNP_EINVAL;
+  if (!(alpha > 0.0f && alpha <= 1.0f) || !(eps > 0.0f && eps < 1.0f)) return APPNP_EINVAL;
+  if (b == 0 || g->n == 0) return APPNP_OK;
+  const int64_t n = g->n;
+  if (!sources || !X || !ws || n > INT32_MAX || b > INT32_MAX) return APPNP_EINVAL;
+  if (ws_bytes < appnp_push_workspace_bytes(n, b)) return APPNP_EINVAL;
+  if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return APPNP_EINVAL;
+  if (g->row_lo != 0 || g->row_hi != n) return APPNP_ENOTSUP;  // needs the whole graph
+  if (!g->symmetric) return APPNP_ENOTSUP;
+  const bool sym = g->mode == APPNP_NORM_SYM;
+  if (!sym && !g->t_row_ptr) return APPNP_ENOTSUP;  // rw: the columns of A_hat are rows of A_hat^T
+
+  PushArgs a{};
+  a.row_ptr = sym ? g->row_ptr : g->t_row_ptr;
+  a.col = sym ? g->col : g->t_col;
+  a.val = sym ? g->val : g->t_val;
+  a.dinv = sym ? g->dinv : nullptr;
+  a.sources = sources;
+  a.n = n;
+  a.b = b;
+  a.alpha = alpha;
+  a.beta = 1.0f - alpha;
+  a.eps = eps;
+  a.max_rounds = max_rounds;
+  char* base = static_cast<char*>(ws);
+  a.thr = sym ? reinterpret_cast<int64_t*>(base) : nullptr;
+  a.r = reinterpret_cast<int64_t*>(base + thr_bytes(n));
+  a.p = a.r + n * b;
+  a.take = a.p + n * b;
+  a.lists = reinterpret_cast<int32_t*>(a.take + n * b);
+  a.rounds = rounds;
+  a.left = left;
+  a.x = X;
+  a.ld_x = ld_x;
+  const int64_t jt = (n + kEmitTile - 1) / kEmitTile, ct = (b + kEmitTile - 1) / kEmitTile;
+  // the emit launch: grid.y, and HIP bounds a grid's threads by 2^32
+  if (ct > 65535 || jt * ct > (((int64_t)1 << 32) - 1) / kBlock) return APPNP_ERANGE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  // r and p are adjacent and 256-byte aligned: 2 n b int64 = n b 16-byte stores
+  const int64_t n16 = n * b;
+  const unsigned clear_grid = (unsigned)std::min<int64_t>((n16 + kBlock - 1) / kBlock, 1 << 16);
+  int rc = timed_launch(s, APPNP_KT_COPY, [&] {
+    hipLaunchKernelGGL(k_push_clear, dim3(clear_grid), dim3(kBlock), 0, s,
+                       reinterpret_cast<ulonglong2*>(a.r), n16);
+  });
+  if (rc == APPNP_OK && sym)
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
+      hipLaunchKernelGGL(k_push_thr, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                         s, a);
+    });
+  if (rc == APPNP_OK)
+    rc = timed_launch(s, APPNP_KT_PUSH, [&] {
+      hipLaunchKernelGGL(k_push, dim3((unsigned)b), dim3(kPushBlock), 0, s, a);
+    });
+  if (rc == APPNP_OK)
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
+      hipLaunchKernelGGL(k_push_emit, dim3((unsigned)jt, (unsigned)ct), dim3(kBlock), 0, s, a);
+    });
+  return rc;
+}

@@ -193,19 +193,22 @@ class APPNP(nn.Module):
             self._ppr = (key, P)
         return self._ppr[1]
 
-    def sparse_ppr(self, topk: int, tol: float | None = None):
+    def sparse_ppr(self, topk: int, tol: float | None = None, eps: float | None = None,
+                   info: list | None = None):
         """The sparsified PPR matrix of batch-main.py:115-116 as an N x N ``SparsePPR``
         (ppr.sparsified_ppr: top ``topk`` of every column, N * topk entries, no N x N matrix),
         for ``P.batch(idx_batch)`` / ``P.rows(idx)`` and ``forward(X, ppr=...)``.  The columns
-        come from the same series as ``ppr`` or, with ``tol``, from the exact solver.  Cached
-        per (device, topk, tol)."""
+        come from the same series as ``ppr``, with ``tol`` from the exact solver, or with ``eps``
+        from forward push (``info`` then receives the push's (rounds, left) tensors per chunk,
+        when the matrix is built).  Cached per (device, topk, tol, eps)."""
         from .ppr import sparsified_ppr
 
         g = self.graph()
-        key = (g.device, int(topk), tol)
+        key = (g.device, int(topk), tol, eps)
         if self._sparse_ppr is None or self._sparse_ppr[0] != key:
             K = int(math.ceil(math.log(self.PPR_TOL) / math.log(1.0 - self.alpha)))
-            self._sparse_ppr = (key, sparsified_ppr(g, int(topk), K, self.alpha, tol=tol))
+            self._sparse_ppr = (key, sparsified_ppr(g, int(topk), K, self.alpha, tol=tol,
+                                                     eps=eps, info=info))
         return self._sparse_ppr[1]
 
     def get_norm(self):

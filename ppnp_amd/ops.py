@@ -272,6 +272,48 @@ def topk_columns(X: torch.Tensor, k: int, row_scale: torch.Tensor | None = None,
     return idx, val
 
 
+# ---- PPR columns by local forward push (appnp_push_columns) --------------------------------
+
+
+def push_columns(graph: Graph, idx, alpha: float = 0.1, eps: float = 1e-4,
+                 max_rounds: int = 1000, out: torch.Tensor | None = None):
+    """Pi[:, idx] by forward push via ``appnp_push_columns``: ``(X fp32 [n, B], rounds int32 [B],
+    left int32 [B])``.  A source's residual is pushed only where it has reached ``eps * w_j``
+    (w_j = sqrt(d_j) for 'sym', 1 for 'rw'), in int64 fixed point, so the work per source follows
+    1 / eps and its neighbourhood, not n, and X is bitwise reproducible.  ``left[c] == 0`` means
+    column c ended with an empty frontier and |Pi[j, s] - X[j, c]| < eps * w_j holds;
+    ``left[c] > 0``: ``max_rounds`` cut it short; ``-1``: ``idx[c]`` lies outside [0, n) (a zero
+    column).  ``out``: an fp32 [n, B] tensor with unit column stride to write into (a padded
+    leading dimension is passed through, the padding is not touched).  Undirected full graphs;
+    'rw' needs the transpose (``Graph.from_scipy(..., transpose=True)``).  Stream-ordered on the
+    current stream, no host synchronisation; see include/ppnp_amd.h."""
+    if not graph.symmetric:
+        raise ValueError("push_columns needs an undirected graph (symmetric A)")
+    if graph.row_lo != 0 or graph.row_hi != graph.n:
+        raise ValueError("push_columns needs a full (not row-partitioned) graph")
+    idx = torch.as_tensor(idx, device=graph.device).long().contiguous().reshape(-1)
+    n, b = graph.n, int(idx.numel())
+    X = torch.empty(n, b, dtype=torch.float32, device=graph.device) if out is None else out
+    if X.dtype != torch.float32 or X.device != graph.device or tuple(X.shape) != (n, b):
+        raise ValueError(f"out must be float32 [{n}, {b}] on {graph.device}")
+    if b > 0 and n > 0 and X.stride(1) != 1:
+        raise ValueError("out must have unit column stride")
+    rounds = torch.zeros(b, dtype=torch.int32, device=graph.device)
+    left = torch.zeros(b, dtype=torch.int32, device=graph.device)
+    lib = _lib.load()
+    ws_bytes = int(lib.appnp_push_workspace_bytes(n, b))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    with torch.cuda.device(graph.device):
+        rc = lib.appnp_push_columns(graph.handle, _vp(idx), b, float(alpha), float(eps),
+                                    int(max_rounds), _vp(X), max(_ld(X), b), _vp(rounds),
+                                    _vp(left), _vp(ws), ws_bytes, _stream(graph.device))
+    if rc == _lib.APPNP_ENOTSUP and graph.mode == "rw":
+        raise ValueError("push_columns on an 'rw' graph walks A_hat^T: build the graph with "
+                         "transpose=True (Graph.from_scipy(..., transpose=True))")
+    _lib.check("appnp_push_columns", rc)
+    return X, rounds, left
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:
@@ -430,7 +472,8 @@ class SolvePlan(PropagatePlan):
 
 
 KERNEL_KINDS = {_lib.KT_COPY: "copy", _lib.KT_STEP: "step", _lib.KT_REM: "rem",
-                _lib.KT_LOCAL: "local", _lib.KT_REMOTE: "remote", _lib.KT_XCHG: "xchg"}
+                _lib.KT_LOCAL: "local", _lib.KT_REMOTE: "remote", _lib.KT_XCHG: "xchg",
+                _lib.KT_PUSH: "push"}
 
 
 def kernel_times(fn, device, max_launches: int = 1024) -> list[tuple[str, float]]:
@@ -438,8 +481,9 @@ def kernel_times(fn, device, max_launches: int = 1024) -> list[tuple[str, float]
     ``_end``) and return one (kind, ms) pair per launch it enqueued, in launch order: "copy"
     (the split copy), "step" (the SpMM kernel), "local" / "remote" (its two halves on a
     row-partitioned graph), "rem" (the remainder pass), "xchg" (an exchange of the library's
-    own row loop).  Each interval is bracketed by events right before and after its launch on
-    the launch stream, so no wait before it is counted; no profiler runs."""
+    own row loop), "push" (the forward-push launch of ``push_columns``).  Each interval is
+    bracketed by events right before and after its launch on the launch stream, so no wait
+    before it is counted; no profiler runs."""
     lib = _lib.load()
     with torch.cuda.device(device):
         # fn() runs even if the timer cannot start: at N > 1 it may hold collectives that every

@@ -22,6 +22,11 @@ the reference's own limit.
 for a chunk of source nodes (``ppr_columns``), reduced on the device to each column's k largest
 entries by ``ops.topk_columns`` (``appnp_topk_columns``), kept as a device CSR (``SparsePPR``).
 ``SparsePPR.batch`` is the minibatch wrapper batch-main.py:136-138 asks for.
+
+The columns come from one of three routes: the K-step series (default), the Chebyshev solver
+(``tol=``), or local forward push (``eps=``, ``ops.push_columns``: work per source that follows
+1 / eps and the source's neighbourhood instead of N -- the route for large graphs).  Everything
+after the columns is the same for all three.
 """
 
 from __future__ import annotations
@@ -29,7 +34,8 @@ from __future__ import annotations
 import torch
 
 from .graph import Graph
-from .ops import propagate_forward, solve_forward, solve_iterations, topk_columns
+from .ops import (propagate_forward, push_columns, solve_forward, solve_iterations,
+                  topk_columns)
 from .sparse import SparseFeatures
 
 
@@ -39,11 +45,27 @@ def _degrees(graph: Graph):
     return 1.0 / dinv
 
 
+def _one_route(tol, eps):
+    if tol is not None and eps is not None:
+        raise ValueError("tol= (the solver's columns) and eps= (forward push) are mutually "
+                         "exclusive")
+
+
 def ppr_columns(graph: Graph, idx: torch.Tensor, K: int = 10, alpha: float = 0.1,
-                tol: float | None = None):
+                tol: float | None = None, eps: float | None = None, max_rounds: int = 1000,
+                info: list | None = None):
     """Pi[:, idx] (N x B, fp32) = APPNP_K of the one-hot columns of idx; with ``tol`` the exact
-    columns to that relative tolerance by the Chebyshev solver (ops.solve_forward), K ignored."""
+    columns to that relative tolerance by the Chebyshev solver (ops.solve_forward), K ignored;
+    with ``eps`` the forward-push columns (ops.push_columns: |error| < eps sqrt(d_j) for sym, eps
+    for rw), K ignored.  ``tol`` and ``eps`` are mutually exclusive.  ``info``: a list that
+    receives the push's ``(rounds, left)`` device tensors (``left`` all zero: the bound holds)."""
+    _one_route(tol, eps)
     idx = torch.as_tensor(idx, device=graph.device).long()
+    if eps is not None:
+        X, rounds, left = push_columns(graph, idx, alpha, eps, max_rounds)
+        if info is not None:
+            info.append((rounds, left))
+        return X
     B = int(idx.numel())
     E = torch.zeros(graph.n, B, dtype=torch.float32, device=graph.device)
     E[idx, torch.arange(B, device=graph.device)] = 1.0
@@ -154,16 +176,19 @@ class SparsePPR(SparseFeatures):
 
 
 def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
-              tol: float | None = None, chunk: int = 128) -> SparsePPR:
+              tol: float | None = None, chunk: int = 128, eps: float | None = None,
+              max_rounds: int = 1000, info: list | None = None) -> SparsePPR:
     """Pi[idx, :] reduced to each row's k largest entries, as a SparsePPR [len(idx) x N] with
     exactly k entries per row (ties at the k-th value go to the smaller column).  The sources
-    are taken ``chunk`` at a time: their PPR columns (``ppr_columns``: the K-step series, or
-    with ``tol`` the solver's columns) are selected on the device by ``ops.topk_columns``, with
+    are taken ``chunk`` at a time: their PPR columns (``ppr_columns``: the K-step series, with
+    ``tol`` the solver's columns, with ``eps`` the forward-push columns; ``max_rounds`` and
+    ``info`` as there) are selected on the device by ``ops.topk_columns``, with
     no transposed copy and no read-back.  sym: the rows are the columns; rw:
     Pi[i, :] = D * Pi[:, i] / d_i, applied as the kernel's row and column scales.  Memory is
     one N x chunk block plus the len(idx) * k result.  Undirected graphs only."""
     if not graph.symmetric:
         raise ValueError("topk_rows needs an undirected graph (symmetric A)")
+    _one_route(tol, eps)
     idx = torch.as_tensor(idx, device=graph.device).long()
     rs = cs_all = None
     if graph.mode != "sym":
@@ -173,7 +198,7 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
     ix, dv = [], []
     for s in range(0, int(idx.numel()), int(chunk)):
         part = idx[s:s + chunk]
-        cols = ppr_columns(graph, part, K, alpha, tol)
+        cols = ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info)
         i, v = topk_columns(cols, k, rs, None if cs_all is None else cs_all[s:s + chunk])
         ix.append(i.reshape(-1))
         dv.append(v.reshape(-1))
@@ -185,14 +210,16 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
 
 
 def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
-                   tol: float | None = None, chunk: int = 128) -> SparsePPR:
+                   tol: float | None = None, chunk: int = 128, eps: float | None = None,
+                   max_rounds: int = 1000, info: list | None = None) -> SparsePPR:
     """The sparsified Pi of batch-main.py:115-116 as an N x N SparsePPR, without the N x N
     matrix.  That line's broadcasting makes every COLUMN keep its top k,
     so the k largest entries of every column Pi[:, j] are selected chunk by chunk
     (``ppr_columns`` + ``ops.topk_columns``) as a CSC with exactly k entries per column, which
     ``appnp_csr_transpose`` turns into the CSR.  Memory is N * k entries (twice: the CSC stays
     as the cached transpose the backward needs) plus one N x chunk block; the N^2 guard of
-    ``dense_ppr`` does not apply.
+    ``dense_ppr`` does not apply.  ``tol`` / ``eps`` / ``max_rounds`` / ``info``: the route to the
+    columns, as for ``ppr_columns`` (``eps``: forward push, whose work does not grow with N).
 
     One deviation from the reference: it keeps every entry >= the threshold -- more than k on
     ties, and in practice sometimes fewer, because its fp64 inverse is not exactly symmetric and
@@ -201,13 +228,14 @@ def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
     not symmetric, this is the column-wise reading as well."""
     if not graph.symmetric:
         raise ValueError("sparsified_ppr needs an undirected graph (symmetric A)")
+    _one_route(tol, eps)
     n = graph.n
     if n * int(k) >= 2**31:
         raise ValueError("sparsified_ppr: N * k exceeds the int32 CSR index range")
     ix, dv = [], []
     for s in range(0, n, int(chunk)):
         part = torch.arange(s, min(n, s + chunk), device=graph.device)
-        i, v = topk_columns(ppr_columns(graph, part, K, alpha, tol), k)
+        i, v = topk_columns(ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info), k)
         ix.append(i.reshape(-1))
         dv.append(v.reshape(-1))
     indptr = torch.arange(n + 1, dtype=torch.int64, device=graph.device) * int(k)

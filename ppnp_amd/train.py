@@ -19,7 +19,8 @@ the reference; tests/test_train.py pins them to the reference's own outputs.
 
 With ``--batch-size B --ppr-topk k`` (``--model appnp``) it follows the reference's second entry
 point, batch-main.py:104-169, instead: minibatches of top-k-sparsified PPR rows, on the sparse
-matrix of ``APPNP.sparse_ppr`` (no N x N matrix; ppnp_amd/ppr.py).
+matrix of ``APPNP.sparse_ppr`` (no N x N matrix; ppnp_amd/ppr.py).  ``--ppr-eps 1e-4`` builds
+those rows by forward push, whose work per source does not grow with N.
 """
 
 from __future__ import annotations
@@ -226,7 +227,15 @@ def _run_batches(model, opt, early_stopping, X, idx, y, args, stats=None):
     loader = DataLoader(TensorDataset(idx_train.cpu(), y_train.cpu()),
                         batch_size=args.batch_size, shuffle=True, num_workers=0)
     t0 = time.time()
-    P = model.sparse_ppr(args.ppr_topk, tol=args.tol if args.exact else None)
+    eps = getattr(args, "ppr_eps", None)
+    info = []
+    P = model.sparse_ppr(args.ppr_topk, tol=args.tol if args.exact and eps is None else None,
+                         eps=eps, info=info)
+    if info:  # forward push: every column must have ended with an empty frontier (one read-back)
+        left = torch.cat([l for _, l in info])
+        if bool((left != 0).any()):
+            raise RuntimeError(f"--ppr-eps {eps}: {int((left != 0).sum())} PPR columns did not "
+                               "finish their forward push (max_rounds reached)")
     torch.cuda.synchronize()
     if stats is not None:
         stats["ppr_build"] = time.time() - t0
@@ -299,6 +308,10 @@ def parse_args(argv=None):
                         "(batch-main.py); needs --ppr-topk")
     p.add_argument("--ppr-topk", type=int, default=None,
                    help="entries kept per column of the PPR matrix (batch-main.py:115-116)")
+    p.add_argument("--ppr-eps", type=float, default=None,
+                   help="build the sparsified PPR rows by forward push to this threshold "
+                        "(ops.push_columns) instead of the series / the solver; needs "
+                        "--batch-size")
     p.add_argument("--test", action="store_true")
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
@@ -310,8 +323,12 @@ def parse_args(argv=None):
         if args.sparse_x:
             p.error("--batch-size cannot be combined with --sparse-x: a minibatch takes the "
                     "rows X[sel], which needs a dense X")
+        if args.ppr_eps is not None and not 0.0 < args.ppr_eps < 1.0:
+            p.error("--ppr-eps must lie in (0, 1)")
     elif args.ppr_topk is not None:
         p.error("--ppr-topk needs --batch-size")
+    elif args.ppr_eps is not None:
+        p.error("--ppr-eps needs --batch-size and --ppr-topk")
     if "ms_academic" in args.dataset:  # main.py:56-59
         args.alpha = 0.2
         args.nknown = 5000
@@ -337,6 +354,8 @@ def main(argv=None):
                "epochs_mean": float(np.mean([r["epoch"] for r in records])),
                "elapsed_mean": float(np.mean([r["elapsed"] for r in records]))}
     if args.batch_size:
+        if args.ppr_eps is not None:
+            summary["ppr_eps"] = args.ppr_eps
         summary.update({"batch_size": args.batch_size, "ppr_topk": args.ppr_topk,
                         "ppr_build_mean": float(np.mean(builds)),
                         "records": records})
