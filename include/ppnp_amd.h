@@ -50,7 +50,8 @@ extern "C" {
  * appnp_solve_iterations, appnp_solve_weights, appnp_solve, appnp_solve_bwd and
  * appnp_plan_create_solve; the column top-k selection appnp_topk_workspace_bytes and
  * appnp_topk_columns; PPR columns by forward push, appnp_push_workspace_bytes and
- * appnp_push_columns, with the timer kind APPNP_KT_PUSH. */
+ * appnp_push_columns, with the timer kind APPNP_KT_PUSH; the top k straight from the push,
+ * appnp_push_topk_workspace_bytes and appnp_push_topk. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -365,6 +366,51 @@ size_t appnp_push_workspace_bytes(int64_t n, int64_t b);
 int appnp_push_columns(const appnp_graph* g, const int64_t* sources, int64_t b, float alpha,
                        float eps, int max_rounds, float* X, int64_t ld_x, int32_t* rounds,
                        int32_t* left, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * Sparse top-k PPR rows straight from the forward push: what appnp_push_columns followed by
+ * appnp_topk_columns gives for the same arguments -- the same out_idx (ascending, exactly k per
+ * source), the same bits in out_val, the same rounds and left -- without the dense n x b block.
+ * The cost per source follows the push alone (about 1 / eps and the local neighbourhood), from
+ * the push to the CSR row, and the workspace depends on `slots`, not on b: one call can take any
+ * number of sources, all n of them included.
+ *
+ * The push is appnp_push_columns' (same fixed point, rounds and thresholds).  The candidate of
+ * (node j, source c) is v = (X * row_scale[j]) * col_scale[c] with X = (float)((double)p_j 2^-44),
+ * two separately rounded fp32 products, a NULL scale meaning no multiplication; the order is
+ * appnp_topk_columns' (larger v first, equal v to the smaller j), taken on v, not on p.  Only the
+ * nodes the push took can have p > 0.  A source with fewer than k positive candidates is filled
+ * with +0.0 at the smallest indices that hold none, as the chain does; an index outside [0, n)
+ * gives the indices 0 .. k-1 with +0.0 and left = -1.  The identity with the chain holds for
+ * scales that are finite and > 0 (the degrees and inverse degrees of 'rw'); with other scales
+ * the chain's candidates of untouched nodes are no longer +0.0 and the result is unspecified.
+ *
+ *   k: 1 .. min(n, APPNP_PUSH_TOPK_MAX_K); out_idx / out_val: [b, k], ld_out >= k, elements
+ *      j >= k of a row are not written.
+ *   slots: workgroups (of 1024 threads) launched; workgroup w runs the sources w, w + slots, ...
+ *      in order on its own slice of the workspace and leaves it clean for the next one, at the
+ *      cost of one more walk over the rows of the nodes it took.  min(slots, b) are used.
+ *   ws: appnp_push_topk_workspace_bytes(n, slots) bytes (monotone in n and slots, 0 for an empty
+ *      shape), 16-byte aligned: per slot r, p and the takes as int64 [n] and three lists of
+ *      capacity n as int32 (36 n bytes), plus the n thresholds.
+ * Launches on `stream`: one clear of the slots' r and p and the thresholds ('sym') as
+ * APPNP_KT_COPY, then ONE launch with the push, the selection (a workgroup-local radix select on
+ * the 64-bit keys order_key(v) << 32 | ~j) and the clean-up of every source, as APPNP_KT_PUSH.
+ * No workgroup waits for another; integer atomics only, so two runs give the same bits.
+ * Stream-ordered, no allocation, no host synchronisation, no read-back, graph-capturable.
+ * APPNP_EINVAL, before any device call: a NULL g, b < 0, k < 1, ld_out < k, max_rounds < 1,
+ * slots < 1, alpha outside (0, 1], eps outside (0, 1); then APPNP_OK when b == 0 or n == 0; then
+ * APPNP_EINVAL for k > n, a NULL sources / out_idx / out_val / ws or ws_bytes too small.
+ * APPNP_ENOTSUP: a row-partitioned graph, a graph whose symmetric flag is 0, 'rw' without the
+ * transpose, k > APPNP_PUSH_TOPK_MAX_K.  fp32 only.
+ */
+#define APPNP_PUSH_TOPK_MAX_K 1024
+size_t appnp_push_topk_workspace_bytes(int64_t n, int slots);
+int appnp_push_topk(const appnp_graph* g, const int64_t* sources, int64_t b, float alpha,
+                    float eps, int max_rounds, int k, const float* row_scale,
+                    const float* col_scale, int32_t* out_idx, float* out_val, int64_t ld_out,
+                    int32_t* rounds, int32_t* left, int slots, void* ws, size_t ws_bytes,
+                    void* stream);
 
 /*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]

@@ -107,6 +107,12 @@ _SIGS = {
         _i32,
         [_vp, _vp, _i64, _f32, _f32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
     ),
+    "appnp_push_topk_workspace_bytes": (_sz, [_i64, _i32]),
+    "appnp_push_topk": (
+        _i32,
+        [_vp, _vp, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp,
+         _sz, _vp],
+    ),
     "appnp_plan_launch": (_i32, [_vp, _vp]),
     "appnp_plan_destroy": (None, [_vp]),
     "appnp_dist_create": (

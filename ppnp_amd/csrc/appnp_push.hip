@@ -27,9 +27,13 @@
 // round.  r is accessed by 64-bit integer atomics only; the lists and takes are plain stores read
 // after a workgroup barrier.  The launches on `stream`: clear of r and p, thresholds (sym),
 // push, emit (p -> X through an LDS transpose, coalesced on both sides).
+//
+// appnp_push_topk (further down) runs the same push on a grid of reusable slots
+// and selects each source's top k straight from the nodes it took: no dense block.
 #include <algorithm>
 
 #include "appnp_internal.h"
+#include "appnp_topk_key.h"  // order_key
 #include "../../include/ppnp_amd.h"
 
 namespace appnp {
@@ -173,6 +177,293 @@ __global__ __launch_bounds__(kBlock) void k_push_emit(PushArgs a) {
   }
 }
 
+// ---- appnp_push_topk: the push, then the top k straight from the list of taken nodes ----------
+//
+// A grid of SLOTS: workgroup w runs the sources w, w + slots, ... one after another on its own
+// slice of the workspace (r, p, take as int64 [n], two frontier lists and the list of the distinct
+// nodes taken so far as int32 [n]).  Per source:
+//   push     the loop of k_push; the take phase also sets kSeen in p_i (fetch_or) and the one
+//            thread that found it unset appends i to the taken list: once per node, whatever the
+//            increments of p_i truncate to
+//   keys     per taken node the candidate v = ((float)(p 2^-44) * row_scale) * col_scale and, when
+//            v > 0, the composite key order_key(v) << 32 | ~i (all distinct: the tie rule is part
+//            of the key), written over the take slab; 0 otherwise
+//   select   with more than k positive candidates, a radix select in LDS (8 bits per pass from the
+//            top; it stops at the first digit whose bin holds exactly what is still wanted) finds
+//            T with exactly k keys >= T; otherwise every positive candidate wins (T = 1)
+//   emit     winners compacted into LDS; a short row is filled with +0.0 at the smallest indices
+//            of [0, k) that hold no winner (flags over [0, k) and a scan); every entry's place is
+//            the number of entries with a smaller index
+//   clean    r_j = 0 over the rows of the taken nodes, p_i = r_i = 0 of those nodes, r_s = 0: every
+//            nonzero of the slot, at the cost of one more walk of what the push walked (skipped
+//            after a slot's last source: every call starts with a clear of r and p)
+// r and p are accessed by relaxed agent-scope atomics only (a slot is reused inside one launch; a
+// plain load could hit a line cached from the source before).  Lists, takes and keys are plain
+// stores read after a workgroup barrier.  No workgroup waits for or reads from another one.
+
+constexpr int kTopkCap = kPushBlock;          // k <= 1024: a thread per output entry
+constexpr int64_t kSeen = (int64_t)1 << 62;   // in p_i: node i is on the taken list (p < 2^45)
+
+struct PushTopkArgs {
+  const int32_t* row_ptr;  // A_hat^T, as PushArgs
+  const int32_t* col;
+  const float* val;
+  const int64_t* sources;
+  const float* row_scale;  // [n] or null
+  const float* col_scale;  // [b] or null
+  int64_t n, b;
+  float alpha, beta;
+  float eps;
+  int max_rounds;
+  int k;
+  const int64_t* thr;      // [n] (sym only)
+  int64_t* r;              // [slots][n]
+  int64_t* p;              // [slots][n]
+  int64_t* take;           // [slots][n]: the takes of a round, then the keys of the select
+  int32_t* lists;          // [slots][3][n]: two frontier lists, the taken list
+  int32_t* rounds;
+  int32_t* left;
+  int32_t* out_idx;
+  float* out_val;
+  int64_t ld_out;
+};
+
+__device__ __forceinline__ int64_t load_i64(const int64_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void store_i64(int64_t* p, int64_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kPushBlock) void k_push_topk(PushTopkArgs a) {
+  __shared__ int cnt[2];
+  __shared__ int ntaken, npos, nwin;
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t pick[3];  // the digit found, the keys above its bin, the keys in its bin
+  __shared__ int wsum[kPushWaves];
+  __shared__ int32_t widx[kTopkCap];
+  __shared__ float wval[kTopkCap];
+  __shared__ int flag[kTopkCap];
+  const int64_t n = a.n;
+  const int k = a.k;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const int64_t slot = blockIdx.x;
+  int64_t* r = a.r + slot * n;
+  int64_t* p = a.p + slot * n;
+  int64_t* take = a.take + slot * n;
+  int32_t* list = a.lists + 3 * slot * n;
+  int32_t* taken = list + 2 * n;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(take);
+  const int64_t thr_rw = threshold(a.eps, 1.0);
+  const double alpha = (double)a.alpha, beta = (double)a.beta;
+
+  for (int64_t c = slot; c < a.b; c += gridDim.x) {
+    const int64_t s = a.sources[c];
+    const bool valid = s >= 0 && s < n;
+    if (tid == 0) {
+      ntaken = 0;
+      npos = 0;
+      nwin = 0;
+      cnt[0] = 0;
+      cnt[1] = 0;
+      if (valid) {
+        const int64_t thr_s = a.thr ? a.thr[s] : thr_rw;
+        store_i64(r + s, kOne);
+        list[0] = (int32_t)s;
+        cnt[0] = kOne >= thr_s ? 1 : 0;
+      }
+    }
+    if (tid < k) flag[tid] = 0;
+    __syncthreads();
+
+    // ---- push: k_push's loop; the take phase records a node the first time it is taken
+    int cur = 0, round = 0;
+    int64_t m = 0;
+    for (;;) {
+      m = std::min<int64_t>((int64_t)cnt[cur], n);
+      if (m == 0 || round == a.max_rounds) break;
+      if (tid == 0) cnt[cur ^ 1] = 0;
+      int32_t* fl = list + (int64_t)cur * n;
+      int32_t* nl = list + (int64_t)(cur ^ 1) * n;
+      for (int64_t q = tid; q < m; q += kPushBlock) {
+        const int64_t i = fl[q];
+        const int64_t t =
+            __hip_atomic_exchange(r + i, (int64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        take[q] = t;
+        const int64_t seen =
+            __hip_atomic_fetch_or(p + i, kSeen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!(seen & kSeen)) {  // exactly one thread per node, ever: at most n appends
+          const int pos = atomicAdd(&ntaken, 1);
+          if (pos < n) taken[pos] = (int32_t)i;
+        }
+        fetch_add(p + i, (int64_t)((double)t * alpha));
+      }
+      __syncthreads();  // every take before every add
+      const bool together = m < kPushWaves;
+      const int64_t q0 = together ? 0 : wave, dq = together ? 1 : kPushWaves;
+      const int off = (together ? wave * kWave : 0) + lane;
+      const int step = together ? kPushBlock : kWave;
+      for (int64_t q = q0; q < m; q += dq) {
+        const int64_t i = fl[q];
+        const double t = (double)take[q];
+        const int64_t e1 = a.row_ptr[i + 1];
+        for (int64_t e = (int64_t)a.row_ptr[i] + off; e < e1; e += step) {
+          const int64_t j = a.col[e];
+          const int64_t add = (int64_t)((t * (double)a.val[e]) * beta);
+          if (j < 0 || j >= n) continue;  // never with a graph this library built
+          const int64_t old = fetch_add(r + j, add);
+          const int64_t th = a.thr ? a.thr[j] : thr_rw;
+          if (old < th && old + add >= th) {
+            const int pos = atomicAdd(&cnt[cur ^ 1], 1);
+            if (pos < n) nl[pos] = (int32_t)j;
+          }
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+      ++round;
+    }
+    if (tid == 0) {
+      if (a.rounds) a.rounds[c] = round;
+      if (a.left) a.left[c] = valid ? (int32_t)m : -1;
+    }
+    // the last barrier passed (the loop's, or the one before it) ordered every append
+    const int64_t L = std::min<int64_t>((int64_t)ntaken, n);
+
+    // ---- keys: over the take slab, which the push no longer reads
+    {
+      const bool has_cs = a.col_scale != nullptr;
+      const float cs = has_cs ? a.col_scale[c] : 1.0f;
+      for (int64_t q0 = 0; q0 < L; q0 += kPushBlock) {  // whole waves: the ballot below
+        const int64_t q = q0 + tid;
+        bool positive = false;
+        if (q < L) {
+          const int64_t i = taken[q];
+          const int64_t pv = load_i64(p + i) & ~kSeen;
+          float v = (float)((double)pv * kUnit);
+          if (a.row_scale) v = v * a.row_scale[i];
+          if (has_cs) v = v * cs;
+          const uint32_t key = order_key(v);
+          positive = key > kOrderKeyZero;
+          keys[q] = positive ? ((uint64_t)key << 32) | (uint64_t)(~(uint32_t)i) : 0ull;
+        }
+        const unsigned long long mask = __ballot(positive);
+        if (lane == 0 && mask) atomicAdd(&npos, __popcll(mask));
+      }
+    }
+    __syncthreads();
+
+    // ---- select: T with exactly min(k, positives) keys >= T
+    uint64_t T = 1ull;
+    if (npos > k) {
+      uint64_t prefix = 0ull;
+      uint32_t want = (uint32_t)k;
+      for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        if (tid < 256) hist[tid] = 0u;
+        __syncthreads();
+        for (int64_t q = tid; q < L; q += kPushBlock) {
+          const uint64_t key = keys[q];
+          const bool match = pass == 0 || ((key ^ prefix) >> ((shift + 8) & 63)) == 0ull;
+          if (match) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (wave == 0) {  // the digit in which the want-th largest matching key lies
+          const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2],
+                         h3 = hist[4 * lane + 3];
+          const uint32_t own = h0 + h1 + h2 + h3;
+          uint32_t suf = own;  // inclusive suffix sum over lanes >= lane
+#pragma unroll
+          for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t t = __shfl_down(suf, o, kWave);
+            if (lane + o < kWave) suf += t;
+          }
+          uint32_t above = suf - own;
+          if (above < want && want <= suf) {  // exactly one lane
+            uint32_t d = 3, in = h3;
+            if (above + h3 < want) {
+              above += h3; d = 2; in = h2;
+              if (above + h2 < want) {
+                above += h2; d = 1; in = h1;
+                if (above + h1 < want) { above += h1; d = 0; in = h0; }
+              }
+            }
+            pick[0] = 4u * lane + d;
+            pick[1] = above;
+            pick[2] = in;
+          }
+        }
+        __syncthreads();
+        prefix |= (uint64_t)pick[0] << shift;
+        want -= pick[1];
+        // keys are distinct: by the last pass the bin holds one key and one is wanted
+        if (pick[2] == want) break;  // the whole bin wins
+      }
+      T = prefix;
+    }
+
+    // ---- emit: winners into LDS, the padding of a short row, places by index
+    for (int64_t q = tid; q < L; q += kPushBlock) {
+      const uint64_t key = keys[q];
+      if (key >= T) {
+        const int pos = atomicAdd(&nwin, 1);
+        if (pos < k) {  // holds by construction; the guard keeps the store in bounds
+          const uint32_t j = ~(uint32_t)key;
+          widx[pos] = (int32_t)j;
+          wval[pos] = __uint_as_float((uint32_t)(key >> 32) & 0x7fffffffu);  // v > 0
+          if (j < (uint32_t)k) flag[j] = 1;
+        }
+      }
+    }
+    __syncthreads();
+    const int w = std::min(nwin, k);
+    if (w < k) {  // the k - w smallest indices of [0, k) without a winner, value +0.0
+      const bool free_j = tid < k && flag[tid] == 0;
+      const unsigned long long mask = __ballot(free_j);
+      if (lane == 0) wsum[wave] = __popcll(mask);
+      __syncthreads();
+      int zr = __popcll(mask & ((1ull << lane) - 1ull));
+      for (int u = 0; u < wave; ++u) zr += wsum[u];
+      if (free_j && zr < k - w) {
+        widx[w + zr] = tid;
+        wval[w + zr] = 0.0f;
+      }
+      __syncthreads();
+    }
+    if (tid < k) {
+      const int32_t mine = widx[tid];
+      int rank = 0;
+      for (int u = 0; u < k; ++u) rank += widx[u] < mine ? 1 : 0;
+      a.out_idx[c * a.ld_out + rank] = mine;
+      a.out_val[c * a.ld_out + rank] = wval[tid];
+    }
+
+    // ---- clean the slot: the rows of the taken nodes hold every nonzero of r.  Not after the
+    // slot's last source: the next call clears r and p itself
+    if (c + gridDim.x < a.b) {
+      const bool together = L < kPushWaves;
+      const int64_t q0 = together ? 0 : wave, dq = together ? 1 : kPushWaves;
+      const int off = (together ? wave * kWave : 0) + lane;
+      const int step = together ? kPushBlock : kWave;
+      for (int64_t q = q0; q < L; q += dq) {
+        const int64_t i = taken[q];
+        const int64_t e1 = a.row_ptr[i + 1];
+        for (int64_t e = (int64_t)a.row_ptr[i] + off; e < e1; e += step) {
+          const int64_t j = a.col[e];
+          if (j >= 0 && j < n) store_i64(r + j, 0);
+        }
+        if (off == 0) {
+          store_i64(p + i, 0);
+          store_i64(r + i, 0);
+        }
+      }
+      if (tid == 0 && valid) store_i64(r + s, 0);  // a source that ran no round, or no self loop
+    }
+    __syncthreads();  // the slot and the LDS state are free for the next source
+  }
+}
+
 inline size_t round_up(size_t x, size_t al) { return (x + al - 1) / al * al; }
 
 // bytes of the workspace parts: the thresholds, then per source r, p, the takes and two lists
@@ -263,6 +554,87 @@ extern "C" int appnp_push_columns(const appnp_graph* g, const int64_t* sources, 
   if (rc == APPNP_OK)
     rc = timed_launch(s, APPNP_KT_COPY, [&] {
       hipLaunchKernelGGL(k_push_emit, dim3((unsigned)jt, (unsigned)ct), dim3(kBlock), 0, s, a);
+    });
+  return rc;
+}
+
+extern "C" size_t appnp_push_topk_workspace_bytes(int64_t n, int slots) {
+  using namespace appnp;
+  if (n <= 0 || slots <= 0 || n > INT32_MAX) return 0;
+  // per slot r, p, take as int64 [n] and three int32 lists of capacity n; the thresholds once
+  return round_up(thr_bytes(n) + (size_t)36 * (size_t)n * (size_t)slots, 256);
+}
+
+extern "C" int appnp_push_topk(const appnp_graph* g, const int64_t* sources, int64_t b,
+                               float alpha, float eps, int max_rounds, int k,
+                               const float* row_scale, const float* col_scale, int32_t* out_idx,
+                               float* out_val, int64_t ld_out, int32_t* rounds, int32_t* left,
+                               int slots, void* ws, size_t ws_bytes, void* stream) {
+  using namespace appnp;
+  if (!g || b < 0 || k < 1 || ld_out < k || max_rounds < 1 || slots < 1) return APPNP_EINVAL;
+  if (!(alpha > 0.0f && alpha <= 1.0f) || !(eps > 0.0f && eps < 1.0f)) return APPNP_EINVAL;
+  if (b == 0 || g->n == 0) return APPNP_OK;
+  const int64_t n = g->n;
+  if (k > n || !sources || !out_idx || !out_val || !ws || n > INT32_MAX) return APPNP_EINVAL;
+  if (ws_bytes < appnp_push_topk_workspace_bytes(n, slots)) return APPNP_EINVAL;
+  if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) return APPNP_EINVAL;
+  if (g->row_lo != 0 || g->row_hi != n) return APPNP_ENOTSUP;  // needs the whole graph
+  if (!g->symmetric) return APPNP_ENOTSUP;
+  const bool sym = g->mode == APPNP_NORM_SYM;
+  if (!sym && !g->t_row_ptr) return APPNP_ENOTSUP;
+  if (k > APPNP_PUSH_TOPK_MAX_K) return APPNP_ENOTSUP;
+  static_assert(APPNP_PUSH_TOPK_MAX_K == kTopkCap, "the header states the kernel's cap");
+
+  // more slots than sources would only be cleared: the grid is what the sources can fill
+  const int64_t used = std::min<int64_t>(slots, b);
+  char* base = static_cast<char*>(ws);
+  PushTopkArgs a{};
+  a.row_ptr = sym ? g->row_ptr : g->t_row_ptr;
+  a.col = sym ? g->col : g->t_col;
+  a.val = sym ? g->val : g->t_val;
+  a.sources = sources;
+  a.row_scale = row_scale;
+  a.col_scale = col_scale;
+  a.n = n;
+  a.b = b;
+  a.alpha = alpha;
+  a.beta = 1.0f - alpha;
+  a.eps = eps;
+  a.max_rounds = max_rounds;
+  a.k = k;
+  a.thr = sym ? reinterpret_cast<int64_t*>(base) : nullptr;
+  a.r = reinterpret_cast<int64_t*>(base + thr_bytes(n));
+  a.p = a.r + n * used;
+  a.take = a.p + n * used;
+  a.lists = reinterpret_cast<int32_t*>(a.take + n * used);
+  a.rounds = rounds;
+  a.left = left;
+  a.out_idx = out_idx;
+  a.out_val = out_val;
+  a.ld_out = ld_out;
+  PushArgs t{};  // what k_push_thr reads
+  t.dinv = sym ? g->dinv : nullptr;
+  t.n = n;
+  t.eps = eps;
+  t.thr = reinterpret_cast<int64_t*>(base);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  // r and p of the used slots are adjacent and 256-byte aligned: one clear per call, by a kernel
+  // (a captured memset node is not relied on); every source leaves its slot clean
+  const int64_t n16 = n * used;
+  const unsigned clear_grid = (unsigned)std::min<int64_t>((n16 + kBlock - 1) / kBlock, 1 << 16);
+  int rc = timed_launch(s, APPNP_KT_COPY, [&] {
+    hipLaunchKernelGGL(k_push_clear, dim3(clear_grid), dim3(kBlock), 0, s,
+                       reinterpret_cast<ulonglong2*>(a.r), n16);
+  });
+  if (rc == APPNP_OK && sym)
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
+      hipLaunchKernelGGL(k_push_thr, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                         s, t);
+    });
+  if (rc == APPNP_OK)
+    rc = timed_launch(s, APPNP_KT_PUSH, [&] {
+      hipLaunchKernelGGL(k_push_topk, dim3((unsigned)used), dim3(kPushBlock), 0, s, a);
     });
   return rc;
 }

@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "appnp_internal.h"
+#include "appnp_topk_key.h"  // order_key
 #include "../../include/ppnp_amd.h"
 
 namespace appnp {
@@ -60,13 +61,6 @@ struct TopkArgs {
   int64_t ld_out;
   int32_t k;
 };
-
-__device__ __forceinline__ uint32_t order_key(float v) {
-  uint32_t u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;   // NaN: below every number
-  if ((u & 0x7fffffffu) == 0u) u = 0u;              // -0 == +0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // The thread's place: column c of sub-block sb (rows [r0, r1)); false when it has none.
 __device__ __forceinline__ bool my_place(const TopkArgs& a, int64_t& sb, int64_t& c, int64_t& r0,

@@ -194,21 +194,22 @@ class APPNP(nn.Module):
         return self._ppr[1]
 
     def sparse_ppr(self, topk: int, tol: float | None = None, eps: float | None = None,
-                   info: list | None = None):
+                   info: list | None = None, select: str = "block"):
         """The sparsified PPR matrix of batch-main.py:115-116 as an N x N ``SparsePPR``
         (ppr.sparsified_ppr: top ``topk`` of every column, N * topk entries, no N x N matrix),
         for ``P.batch(idx_batch)`` / ``P.rows(idx)`` and ``forward(X, ppr=...)``.  The columns
         come from the same series as ``ppr``, with ``tol`` from the exact solver, or with ``eps``
         from forward push (``info`` then receives the push's (rounds, left) tensors per chunk,
-        when the matrix is built).  Cached per (device, topk, tol, eps)."""
+        when the matrix is built; ``select="lists"`` selects straight from the push's lists in
+        one call, ppr.sparsified_ppr).  Cached per (device, topk, tol, eps, select)."""
         from .ppr import sparsified_ppr
 
         g = self.graph()
-        key = (g.device, int(topk), tol, eps)
+        key = (g.device, int(topk), tol, eps, select)
         if self._sparse_ppr is None or self._sparse_ppr[0] != key:
             K = int(math.ceil(math.log(self.PPR_TOL) / math.log(1.0 - self.alpha)))
             self._sparse_ppr = (key, sparsified_ppr(g, int(topk), K, self.alpha, tol=tol,
-                                                     eps=eps, info=info))
+                                                     eps=eps, info=info, select=select))
         return self._sparse_ppr[1]
 
     def get_norm(self):

@@ -314,6 +314,77 @@ def push_columns(graph: Graph, idx, alpha: float = 0.1, eps: float = 1e-4,
     return X, rounds, left
 
 
+PUSH_TOPK_MAX_K = 1024  # APPNP_PUSH_TOPK_MAX_K of include/ppnp_amd.h
+
+
+def push_topk_slots(graph: Graph, b: int) -> int:
+    """The slot count ``push_topk`` picks for ``b`` sources: one workgroup per compute unit at
+    the most, lowered until the workspace fits a quarter of the free device memory."""
+    slots = max(1, min(int(b), torch.cuda.get_device_properties(graph.device).multi_processor_count))
+    lib = _lib.load()
+    budget = torch.cuda.mem_get_info(graph.device)[0] // 4
+    one = int(lib.appnp_push_topk_workspace_bytes(graph.n, 1))
+    two = int(lib.appnp_push_topk_workspace_bytes(graph.n, 2))
+    per_slot = max(two - one, 1)
+    if int(lib.appnp_push_topk_workspace_bytes(graph.n, slots)) > budget:
+        slots = max(1, min(slots, (budget - one) // per_slot + 1))
+    return slots
+
+
+def push_topk(graph: Graph, idx, k: int, alpha: float = 0.1, eps: float = 1e-4,
+              max_rounds: int = 1000, row_scale: torch.Tensor | None = None,
+              col_scale: torch.Tensor | None = None, slots: int | None = None):
+    """The k largest entries of the forward-push columns Pi[:, idx], straight from the nodes each
+    push took, via ``appnp_push_topk``: ``(idx int32 [B, k], val fp32 [B, k], rounds int32 [B],
+    left int32 [B])``, bit for bit what ``push_columns`` followed by ``topk_columns`` returns for
+    the same arguments, without the dense [n, B] block: the cost per source follows the push, not
+    n.  ``row_scale`` [n] / ``col_scale`` [B]: the selection's scales (finite and > 0).
+    ``slots``: workgroups launched, each running every slots-th source on one reusable slice of
+    the workspace (36 n bytes per slot); None picks ``push_topk_slots``.  One call takes any
+    number of sources.  ``rounds`` / ``left`` and the graph requirements are ``push_columns``'s.
+    Stream-ordered on the current stream, no host synchronisation; see include/ppnp_amd.h."""
+    if not graph.symmetric:
+        raise ValueError("push_topk needs an undirected graph (symmetric A)")
+    if graph.row_lo != 0 or graph.row_hi != graph.n:
+        raise ValueError("push_topk needs a full (not row-partitioned) graph")
+    idx = torch.as_tensor(idx, device=graph.device).long().contiguous().reshape(-1)
+    n, b = graph.n, int(idx.numel())
+    k = int(k)
+    if k < 1 or (n * b > 0 and k > n):
+        raise ValueError(f"k must be in [1, {n}], got {k}")
+    if k > PUSH_TOPK_MAX_K:
+        raise ValueError(f"push_topk selects at most k = {PUSH_TOPK_MAX_K}, got {k}")
+    scales = []
+    for name, t, m in (("row_scale", row_scale, n), ("col_scale", col_scale, b)):
+        if t is not None:
+            if t.dtype != torch.float32 or t.device != graph.device or tuple(t.shape) != (m,):
+                raise ValueError(f"{name} must be float32 [{m}] on {graph.device}")
+            t = t.contiguous()
+        scales.append(t)
+    if slots is None:
+        slots = push_topk_slots(graph, b) if n * b > 0 else 1
+    slots = int(slots)
+    if slots < 1:
+        raise ValueError(f"slots must be at least 1, got {slots}")
+    out_idx = torch.empty(b, k, dtype=torch.int32, device=graph.device)
+    out_val = torch.empty(b, k, dtype=torch.float32, device=graph.device)
+    rounds = torch.zeros(b, dtype=torch.int32, device=graph.device)
+    left = torch.zeros(b, dtype=torch.int32, device=graph.device)
+    lib = _lib.load()
+    ws_bytes = int(lib.appnp_push_topk_workspace_bytes(n, slots))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    with torch.cuda.device(graph.device):
+        rc = lib.appnp_push_topk(graph.handle, _vp(idx), b, float(alpha), float(eps),
+                                 int(max_rounds), k, _vp(scales[0]), _vp(scales[1]),
+                                 _vp(out_idx), _vp(out_val), k, _vp(rounds), _vp(left), slots,
+                                 _vp(ws), ws_bytes, _stream(graph.device))
+    if rc == _lib.APPNP_ENOTSUP and graph.mode == "rw":
+        raise ValueError("push_topk on an 'rw' graph walks A_hat^T: build the graph with "
+                         "transpose=True (Graph.from_scipy(..., transpose=True))")
+    _lib.check("appnp_push_topk", rc)
+    return out_idx, out_val, rounds, left
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:

@@ -26,7 +26,9 @@ entries by ``ops.topk_columns`` (``appnp_topk_columns``), kept as a device CSR (
 The columns come from one of three routes: the K-step series (default), the Chebyshev solver
 (``tol=``), or local forward push (``eps=``, ``ops.push_columns``: work per source that follows
 1 / eps and the source's neighbourhood instead of N -- the route for large graphs).  Everything
-after the columns is the same for all three.
+after the columns is the same for all three.  With ``eps=`` and ``select="lists"`` there are no
+columns at all: ``ops.push_topk`` selects each source's top k straight from the nodes its push
+took, all sources in one call, and returns the same rows bit for bit.
 """
 
 from __future__ import annotations
@@ -34,7 +36,7 @@ from __future__ import annotations
 import torch
 
 from .graph import Graph
-from .ops import (propagate_forward, push_columns, solve_forward, solve_iterations,
+from .ops import (propagate_forward, push_columns, push_topk, solve_forward, solve_iterations,
                   topk_columns)
 from .sparse import SparseFeatures
 
@@ -49,6 +51,16 @@ def _one_route(tol, eps):
     if tol is not None and eps is not None:
         raise ValueError("tol= (the solver's columns) and eps= (forward push) are mutually "
                          "exclusive")
+
+
+def _lists(select, eps) -> bool:
+    """True for select="lists" (ops.push_topk: the top k straight from the push, one call for all
+    sources); it needs the forward-push route."""
+    if select not in ("block", "lists"):
+        raise ValueError(f"select must be 'block' or 'lists', got {select!r}")
+    if select == "lists" and eps is None:
+        raise ValueError("select='lists' selects from the forward push's lists: it needs eps=")
+    return select == "lists"
 
 
 def ppr_columns(graph: Graph, idx: torch.Tensor, K: int = 10, alpha: float = 0.1,
@@ -177,7 +189,8 @@ class SparsePPR(SparseFeatures):
 
 def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
               tol: float | None = None, chunk: int = 128, eps: float | None = None,
-              max_rounds: int = 1000, info: list | None = None) -> SparsePPR:
+              max_rounds: int = 1000, info: list | None = None,
+              select: str = "block") -> SparsePPR:
     """Pi[idx, :] reduced to each row's k largest entries, as a SparsePPR [len(idx) x N] with
     exactly k entries per row (ties at the k-th value go to the smaller column).  The sources
     are taken ``chunk`` at a time: their PPR columns (``ppr_columns``: the K-step series, with
@@ -185,10 +198,15 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
     ``info`` as there) are selected on the device by ``ops.topk_columns``, with
     no transposed copy and no read-back.  sym: the rows are the columns; rw:
     Pi[i, :] = D * Pi[:, i] / d_i, applied as the kernel's row and column scales.  Memory is
-    one N x chunk block plus the len(idx) * k result.  Undirected graphs only."""
+    one N x chunk block plus the len(idx) * k result.  Undirected graphs only.
+
+    ``select="lists"`` (with ``eps``): the same rows, bit for bit, from ONE ``ops.push_topk`` call
+    for all sources, which selects from the nodes each push took and forms no N x chunk block;
+    ``chunk`` is not used and ``info`` receives one ``(rounds, left)`` pair."""
     if not graph.symmetric:
         raise ValueError("topk_rows needs an undirected graph (symmetric A)")
     _one_route(tol, eps)
+    lists = _lists(select, eps)
     idx = torch.as_tensor(idx, device=graph.device).long()
     rs = cs_all = None
     if graph.mode != "sym":
@@ -196,7 +214,13 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
         rs = (1.0 / dinv).float()
         cs_all = dinv[idx].float()
     ix, dv = [], []
-    for s in range(0, int(idx.numel()), int(chunk)):
+    if lists and idx.numel():
+        i, v, rounds, left = push_topk(graph, idx, k, alpha, eps, max_rounds, rs, cs_all)
+        if info is not None:
+            info.append((rounds, left))
+        ix.append(i.reshape(-1))
+        dv.append(v.reshape(-1))
+    for s in ([] if lists else range(0, int(idx.numel()), int(chunk))):
         part = idx[s:s + chunk]
         cols = ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info)
         i, v = topk_columns(cols, k, rs, None if cs_all is None else cs_all[s:s + chunk])
@@ -211,7 +235,8 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
 
 def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
                    tol: float | None = None, chunk: int = 128, eps: float | None = None,
-                   max_rounds: int = 1000, info: list | None = None) -> SparsePPR:
+                   max_rounds: int = 1000, info: list | None = None,
+                   select: str = "block") -> SparsePPR:
     """The sparsified Pi of batch-main.py:115-116 as an N x N SparsePPR, without the N x N
     matrix.  That line's broadcasting makes every COLUMN keep its top k,
     so the k largest entries of every column Pi[:, j] are selected chunk by chunk
@@ -225,15 +250,27 @@ def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
     ties, and in practice sometimes fewer, because its fp64 inverse is not exactly symmetric and
     column j is compared with the threshold of ROW j.  This function keeps exactly k per column,
     by the kernel's tie rule (equal values: the smaller row index first).  For 'rw', where Pi is
-    not symmetric, this is the column-wise reading as well."""
+    not symmetric, this is the column-wise reading as well.
+
+    ``select="lists"`` (with ``eps``): the same CSC, bit for bit, from ONE ``ops.push_topk`` call
+    over all N sources (no N x chunk block, a workspace that follows the slot count); ``chunk``
+    is not used and ``info`` receives one ``(rounds, left)`` pair."""
     if not graph.symmetric:
         raise ValueError("sparsified_ppr needs an undirected graph (symmetric A)")
     _one_route(tol, eps)
+    lists = _lists(select, eps)
     n = graph.n
     if n * int(k) >= 2**31:
         raise ValueError("sparsified_ppr: N * k exceeds the int32 CSR index range")
     ix, dv = [], []
-    for s in range(0, n, int(chunk)):
+    if lists:
+        i, v, rounds, left = push_topk(graph, torch.arange(n, device=graph.device), k, alpha,
+                                       eps, max_rounds)
+        if info is not None:
+            info.append((rounds, left))
+        ix.append(i.reshape(-1))
+        dv.append(v.reshape(-1))
+    for s in ([] if lists else range(0, n, int(chunk))):
         part = torch.arange(s, min(n, s + chunk), device=graph.device)
         i, v = topk_columns(ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info), k)
         ix.append(i.reshape(-1))

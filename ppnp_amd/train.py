@@ -20,7 +20,8 @@ the reference; tests/test_train.py pins them to the reference's own outputs.
 With ``--batch-size B --ppr-topk k`` (``--model appnp``) it follows the reference's second entry
 point, batch-main.py:104-169, instead: minibatches of top-k-sparsified PPR rows, on the sparse
 matrix of ``APPNP.sparse_ppr`` (no N x N matrix; ppnp_amd/ppr.py).  ``--ppr-eps 1e-4`` builds
-those rows by forward push, whose work per source does not grow with N.
+those rows by forward push, whose work per source does not grow with N; ``--ppr-select lists``
+also selects them straight from the push's lists, with no dense block of columns.
 """
 
 from __future__ import annotations
@@ -230,7 +231,7 @@ def _run_batches(model, opt, early_stopping, X, idx, y, args, stats=None):
     eps = getattr(args, "ppr_eps", None)
     info = []
     P = model.sparse_ppr(args.ppr_topk, tol=args.tol if args.exact and eps is None else None,
-                         eps=eps, info=info)
+                         eps=eps, info=info, select=getattr(args, "ppr_select", "block"))
     if info:  # forward push: every column must have ended with an empty frontier (one read-back)
         left = torch.cat([l for _, l in info])
         if bool((left != 0).any()):
@@ -312,6 +313,10 @@ def parse_args(argv=None):
                    help="build the sparsified PPR rows by forward push to this threshold "
                         "(ops.push_columns) instead of the series / the solver; needs "
                         "--batch-size")
+    p.add_argument("--ppr-select", default=None, choices=["block", "lists"],
+                   help="with --ppr-eps: 'lists' selects each source's top k straight from the "
+                        "nodes its push took (ops.push_topk, one call for all sources), 'block' "
+                        "(the default) from dense N x 128 blocks of columns")
     p.add_argument("--test", action="store_true")
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
@@ -329,6 +334,10 @@ def parse_args(argv=None):
         p.error("--ppr-topk needs --batch-size")
     elif args.ppr_eps is not None:
         p.error("--ppr-eps needs --batch-size and --ppr-topk")
+    if args.ppr_select is not None and args.ppr_eps is None:
+        p.error("--ppr-select needs --ppr-eps")
+    if args.ppr_select is None:
+        args.ppr_select = "block"
     if "ms_academic" in args.dataset:  # main.py:56-59
         args.alpha = 0.2
         args.nknown = 5000
@@ -356,6 +365,7 @@ def main(argv=None):
     if args.batch_size:
         if args.ppr_eps is not None:
             summary["ppr_eps"] = args.ppr_eps
+            summary["ppr_select"] = args.ppr_select
         summary.update({"batch_size": args.batch_size, "ppr_topk": args.ppr_topk,
                         "ppr_build_mean": float(np.mean(builds)),
                         "records": records})
