@@ -51,7 +51,9 @@ extern "C" {
  * appnp_plan_create_solve; the column top-k selection appnp_topk_workspace_bytes and
  * appnp_topk_columns; PPR columns by forward push, appnp_push_workspace_bytes and
  * appnp_push_columns, with the timer kind APPNP_KT_PUSH; the top k straight from the push,
- * appnp_push_topk_workspace_bytes and appnp_push_topk. */
+ * appnp_push_topk_workspace_bytes and appnp_push_topk; the per-minibatch slice of a sparse PPR
+ * matrix with its transpose, appnp_csr_batch_workspace_bytes, appnp_csr_batch_count and
+ * appnp_csr_batch_emit. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -411,6 +413,74 @@ int appnp_push_topk(const appnp_graph* g, const int64_t* sources, int64_t b, flo
                     const float* col_scale, int32_t* out_idx, float* out_val, int64_t ld_out,
                     int32_t* rounds, int32_t* left, int slots, void* ws, size_t ws_bytes,
                     void* stream);
+
+/*
+ * The per-minibatch slice of a sparse PPR matrix (batch-main.py:140-142: `ppr_sub = ppr[idx]`,
+ * `sel = (ppr_sub > 0).any(dim=0)`, `ppr_sub[:, sel]`), with the transpose of the sub-matrix: two
+ * calls with ONE read-back between them, the 24 bytes of `counts`, from which the caller sizes the
+ * outputs of the second.
+ *   P: a CSR [rows, cols], int32 indptr / indices, fp32 vals.  indices / vals may be NULL for a
+ *      matrix without entries: every row is then taken as empty.
+ *   idx: b row indices (int64, device memory), in any order, duplicates allowed.  Taken row p is
+ *      P[idx[p]].  An index outside [0, rows) contributes an empty row and is counted in
+ *      counts[2]; the kernels never read outside indptr.
+ *   Column j is SELECTED iff some taken entry (p, j) has val > 0: a stored 0.0, -0.0, negative
+ *      value or NaN does not select its column (nor does an entry whose column lies outside
+ *      [0, cols), which is dropped).  sel: the selected columns, ascending, int64 [n_sel].
+ *   An entry of a taken row is KEPT iff its column is selected, whatever its value.  Kept entries
+ *      keep their order within the row; their column becomes its rank in sel.
+ *   appnp_csr_batch_count writes
+ *      out_indptr: int32 [b + 1], the row pointer of the [b, n_sel] result;
+ *      counts: int64 [3] = kept entries (nnz_out), n_sel, indices outside [0, rows);
+ *   and leaves its state (the bitmap of selected columns and the rank of each of its words) in
+ *   the first appnp_csr_batch_workspace_bytes(cols, b, 0) bytes of ws.
+ *   appnp_csr_batch_emit, after it on the same stream, with nnz_out = counts[0] and
+ *   n_sel = counts[1] and the out_indptr count wrote, reads that state and writes
+ *      out_indices int32 [nnz_out], out_vals fp32 [nnz_out]: the CSR [b, n_sel];
+ *      sel int64 [n_sel];
+ *      t_indptr int32 [n_sel + 1], t_indices int32 [nnz_out], t_vals fp32 [nnz_out]: the
+ *      canonical CSR [n_sel, b] of its transpose, the entries of a row ascending by batch
+ *      position p (equal p: in their order within row p) -- exactly what appnp_csr_transpose
+ *      returns for the sub-matrix, bit for bit.
+ *   Sizes other than those count reported give unspecified values, never an access outside the
+ *   buffers as sized by the arguments.  Outputs of size 0 may be NULL.
+ *   ws: 8-byte aligned; count needs appnp_csr_batch_workspace_bytes(cols, b, 0) bytes, emit
+ *      appnp_csr_batch_workspace_bytes(cols, b, nnz_out).  The size is monotone in each argument
+ *      and 0 for an empty shape (cols <= 0, b <= 0) or a negative nnz_cap.  A caller that knows a
+ *      bound on the kept entries before the read-back passes one workspace to both calls; one that
+ *      does not may run count on a workspace of the smaller size and give emit a larger one that
+ *      starts with a copy of it.  Beyond the bitmap (cols bits) and its word ranks (cols / 32
+ *      words) nothing in it grows with cols: b words, and 8 nnz_cap + 4 min(cols, nnz_cap) bytes.
+ * Launches on `stream`: count is a clear and three kernels (mark the bitmap with atomicOr, for
+ * cols <= APPNP_CSR_BATCH_LDS_COLS gathered in LDS per workgroup before it is merged; count each
+ * taken row; one workgroup that scans the bitmap's popcounts and the row counts,
+ * APPNP_CSR_BATCH_SCAN_PASS items per pass); emit is five (sel; a stable in-row compaction;
+ * t_indptr from per-column counts; a scatter of the kept entries to their column's segment through
+ * an atomic cursor; a sort of each segment by the entry's position in out_indices, which is unique,
+ * so the result does not depend on the order the atomics took).  Work per batch follows the taken
+ * entries plus cols / 32 words.  No workgroup waits for another; integer atomics only, so two runs
+ * give the same bits.  Both calls are stream-ordered and make no allocation and no host
+ * synchronisation.  The per-launch timer records their launches as APPNP_KT_COPY.
+ * APPNP_EINVAL, before any device call: rows, cols or b negative, cols or b > INT32_MAX; for emit
+ * also nnz_out or n_sel negative, nnz_out > INT32_MAX, n_sel > cols, n_sel > nnz_out (every
+ * selected column holds a kept entry).  Then APPNP_OK, with nothing written, when b == 0 or
+ * cols == 0.  Then APPNP_EINVAL for a NULL indptr / idx / out_indptr / ws, a NULL counts (count) or
+ * t_indptr (emit), a NULL array of nnz_out > 0 or n_sel > 0 elements (emit), a workspace that is
+ * too small or not 8-byte aligned.
+ */
+#define APPNP_CSR_BATCH_SCAN_PASS 4096
+#define APPNP_CSR_BATCH_LDS_COLS 131072
+size_t appnp_csr_batch_workspace_bytes(int64_t cols, int64_t b, int64_t nnz_cap);
+int appnp_csr_batch_count(const int32_t* indptr, const int32_t* indices, const float* vals,
+                          int64_t rows, int64_t cols, const int64_t* idx, int64_t b,
+                          int32_t* out_indptr, int64_t* counts, void* ws, size_t ws_bytes,
+                          void* stream);
+int appnp_csr_batch_emit(const int32_t* indptr, const int32_t* indices, const float* vals,
+                         int64_t rows, int64_t cols, const int64_t* idx, int64_t b,
+                         const int32_t* out_indptr, int64_t nnz_out, int64_t n_sel,
+                         int32_t* out_indices, float* out_vals, int64_t* sel, int32_t* t_indptr,
+                         int32_t* t_indices, float* t_vals, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]

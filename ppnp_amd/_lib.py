@@ -113,6 +113,16 @@ _SIGS = {
         [_vp, _vp, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp,
          _sz, _vp],
     ),
+    "appnp_csr_batch_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "appnp_csr_batch_count": (
+        _i32,
+        [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _sz, _vp],
+    ),
+    "appnp_csr_batch_emit": (
+        _i32,
+        [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+         _vp, _sz, _vp],
+    ),
     "appnp_plan_launch": (_i32, [_vp, _vp]),
     "appnp_plan_destroy": (None, [_vp]),
     "appnp_dist_create": (

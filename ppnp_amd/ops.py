@@ -385,6 +385,72 @@ def push_topk(graph: Graph, idx, k: int, alpha: float = 0.1, eps: float = 1e-4,
     return out_idx, out_val, rounds, left
 
 
+# ---- the per-minibatch slice of a sparse PPR matrix (appnp_csr_batch_count / _emit) ---------
+
+CSR_BATCH_SCAN_PASS = 4096  # APPNP_CSR_BATCH_SCAN_PASS of include/ppnp_amd.h
+CSR_BATCH_LDS_COLS = 131072  # APPNP_CSR_BATCH_LDS_COLS
+
+
+def csr_batch(P, idx):
+    """batch-main.py:140-142 on a device CSR ``P`` (a ``SparseFeatures``: int32 ``indptr`` /
+    ``indices``, fp32 ``data``, ``shape``) via ``appnp_csr_batch_count`` / ``_emit``: the rows
+    ``idx`` (int64, any order, duplicates allowed) restricted to the columns ``sel`` in which one
+    of them holds an entry > 0, relabelled into ``sel``.  Returns ``(indptr int32 [b + 1],
+    indices int32, data fp32, sel int64 ascending, (t_indptr, t_indices, t_data))``: the
+    [b x |sel|] CSR, bit for bit what ``SparsePPR.batch`` builds with torch, and the canonical
+    CSR of its transpose, bit for bit ``appnp_csr_transpose`` of it.  One read-back per call (the
+    three counts, 24 bytes) sizes the outputs; everything else is stream-ordered on the current
+    stream.  ``IndexError`` for an index outside [0, rows), ``ValueError`` for 2^31 kept entries
+    or more.  See include/ppnp_amd.h."""
+    dev = P.device
+    if dev.type != "cuda":
+        raise ValueError("csr_batch needs a matrix on a GPU (there is no CPU fallback)")
+    idx = torch.as_tensor(idx, device=dev).long().contiguous().reshape(-1)
+    rows, cols = P.shape
+    b = int(idx.numel())
+    i32 = {"dtype": torch.int32, "device": dev}
+    if b == 0 or cols == 0:  # nothing to select from: the library writes nothing
+        out_indptr = torch.zeros(b + 1, **i32)
+        if b and bool(((idx < 0) | (idx >= rows)).any()):
+            raise IndexError(f"csr_batch: an index lies outside [0, {rows})")
+        empty = torch.empty(0, **i32)
+        return (out_indptr, empty, empty.float(), torch.empty(0, dtype=torch.int64, device=dev),
+                (torch.zeros(1, **i32), empty.clone(), empty.float()))
+    out_indptr = torch.empty(b + 1, **i32)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    head = int(lib.appnp_csr_batch_workspace_bytes(cols, b, 0))
+    ws = torch.empty(head, dtype=torch.uint8, device=dev)
+    src = (_vp(P.indptr), _vp(P.indices), _vp(P.data), rows, cols, _vp(idx), b)
+    with torch.cuda.device(dev):
+        rc = lib.appnp_csr_batch_count(*src, _vp(out_indptr), _vp(counts), _vp(ws), head,
+                                       _stream(dev))
+    _lib.check("appnp_csr_batch_count", rc)
+    nnz, n_sel, bad = counts.cpu().tolist()  # the one read-back: the shapes depend on the data
+    if bad:
+        raise IndexError(f"csr_batch: {bad} of {b} indices lie outside [0, {rows})")
+    if nnz >= 2**31:
+        raise ValueError(f"csr_batch: {nnz} kept entries exceed the int32 CSR index range")
+    # the kept entries are known only now: emit's workspace starts with a copy of count's state
+    need = int(lib.appnp_csr_batch_workspace_bytes(cols, b, nnz))
+    if need > head:
+        ws_emit = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws_emit[:head].copy_(ws)
+        ws = ws_emit
+    out_indices = torch.empty(nnz, **i32)
+    out_vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+    sel = torch.empty(n_sel, dtype=torch.int64, device=dev)
+    t_indptr = torch.empty(n_sel + 1, **i32)
+    t_indices = torch.empty(nnz, **i32)
+    t_vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.appnp_csr_batch_emit(*src, _vp(out_indptr), nnz, n_sel, _vp(out_indices),
+                                      _vp(out_vals), _vp(sel), _vp(t_indptr), _vp(t_indices),
+                                      _vp(t_vals), _vp(ws), int(ws.numel()), _stream(dev))
+    _lib.check("appnp_csr_batch_emit", rc)
+    return out_indptr, out_indices, out_vals, sel, (t_indptr, t_indices, t_vals)
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:

@@ -21,7 +21,9 @@ the reference's own limit.
 ``topk_rows`` / ``sparsified_ppr`` are the same protocol without the N x N matrix: PPR columns
 for a chunk of source nodes (``ppr_columns``), reduced on the device to each column's k largest
 entries by ``ops.topk_columns`` (``appnp_topk_columns``), kept as a device CSR (``SparsePPR``).
-``SparsePPR.batch`` is the minibatch wrapper batch-main.py:136-138 asks for.
+``SparsePPR.batch`` is the minibatch wrapper batch-main.py:136-138 asks for; with
+``slicer="device"`` the slice and its transpose come from ``ops.csr_batch`` (HIP kernels, one
+24-byte read-back per batch) instead of torch operations, bit for bit the same.
 
 The columns come from one of three routes: the K-step series (default), the Chebyshev solver
 (``tol=``), or local forward push (``eps=``, ``ops.push_columns``: work per source that follows
@@ -36,8 +38,8 @@ from __future__ import annotations
 import torch
 
 from .graph import Graph
-from .ops import (propagate_forward, push_columns, push_topk, solve_forward, solve_iterations,
-                  topk_columns)
+from .ops import (csr_batch, propagate_forward, push_columns, push_topk, solve_forward,
+                  solve_iterations, topk_columns)
 from .sparse import SparseFeatures
 
 
@@ -168,11 +170,27 @@ class SparsePPR(SparseFeatures):
         return SparsePPR(self._indptr(lens), self.indices[pos], self.data[pos],
                          (lens.numel(), self.shape[1]), device=self.device)
 
-    def batch(self, idx):
+    def batch(self, idx, slicer: str = "torch"):
         """batch-main.py:140-142 on the sparse form: ``ppr_sub = ppr[idx]``,
         ``sel = (ppr_sub > 0).any(dim=0)``, ``ppr_sub[:, sel]``.  Returns the
         [len(idx) x |sel|] SparsePPR with its columns relabelled into ``sel``, and ``sel`` as the
-        sorted int64 column ids (index X with it: ``X[sel]``)."""
+        sorted int64 column ids (index X with it: ``X[sel]``).
+
+        ``slicer="device"``: the same matrix and ``sel``, bit for bit, from ``ops.csr_batch`` (HIP
+        kernels, one 24-byte read-back per batch), which also emits the transpose: the
+        sub-matrix's ``_t`` is set, so the backward of ``sparse_linear`` does not build it.  GPU
+        matrices only."""
+        if slicer not in ("torch", "device"):
+            raise ValueError(f"slicer must be 'torch' or 'device', got {slicer!r}")
+        if slicer == "device":
+            if self.device.type != "cuda":
+                raise ValueError("slicer='device' needs a matrix on a GPU (there is no CPU "
+                                 "fallback); use slicer='torch'")
+            indptr, indices, data, sel, t = csr_batch(self, idx)
+            sub = SparsePPR(indptr, indices, data, (indptr.numel() - 1, int(sel.numel())),
+                            device=self.device)
+            sub._t = t
+            return sub, sel
         lens, pos = self._take(idx)
         cols, vals = self.indices[pos].long(), self.data[pos]
         sel = torch.unique(cols[vals > 0])  # sorted

@@ -22,6 +22,9 @@ point, batch-main.py:104-169, instead: minibatches of top-k-sparsified PPR rows,
 matrix of ``APPNP.sparse_ppr`` (no N x N matrix; ppnp_amd/ppr.py).  ``--ppr-eps 1e-4`` builds
 those rows by forward push, whose work per source does not grow with N; ``--ppr-select lists``
 also selects them straight from the push's lists, with no dense block of columns.
+``--batch-slice device`` cuts each minibatch out of that matrix with the HIP kernels of
+``ops.csr_batch`` (one 24-byte read-back per batch, the transpose for the backward included)
+instead of torch operations; the numbers are the same bits.
 """
 
 from __future__ import annotations
@@ -245,7 +248,8 @@ def _run_batches(model, opt, early_stopping, X, idx, y, args, stats=None):
     for epoch in range(args.max_epochs):
         model.train()
         for idx_batch, y_batch in loader:
-            ppr_sub, sel = P.batch(idx_batch.to(X.device))
+            ppr_sub, sel = P.batch(idx_batch.to(X.device),
+                                   slicer=getattr(args, "batch_slice", "torch"))
             logits = model(X[sel], idx=None, ppr=ppr_sub)
             loss = F.cross_entropy(logits, y_batch.to(X.device))
             loss = loss + args.reg_lambda / 2 * model.get_norm()
@@ -317,6 +321,11 @@ def parse_args(argv=None):
                    help="with --ppr-eps: 'lists' selects each source's top k straight from the "
                         "nodes its push took (ops.push_topk, one call for all sources), 'block' "
                         "(the default) from dense N x 128 blocks of columns")
+    p.add_argument("--batch-slice", default=None, choices=["torch", "device"],
+                   help="with --batch-size: how a minibatch's rows and columns are cut out of "
+                        "the sparse PPR matrix: 'torch' (the default) with torch operations, "
+                        "'device' with the HIP kernels of ops.csr_batch, which also emit the "
+                        "transpose the backward needs (the same bits either way)")
     p.add_argument("--test", action="store_true")
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
@@ -338,6 +347,10 @@ def parse_args(argv=None):
         p.error("--ppr-select needs --ppr-eps")
     if args.ppr_select is None:
         args.ppr_select = "block"
+    if args.batch_slice is not None and args.batch_size is None:
+        p.error("--batch-slice needs --batch-size")
+    if args.batch_slice is None:
+        args.batch_slice = "torch"
     if "ms_academic" in args.dataset:  # main.py:56-59
         args.alpha = 0.2
         args.nknown = 5000
@@ -367,6 +380,7 @@ def main(argv=None):
             summary["ppr_eps"] = args.ppr_eps
             summary["ppr_select"] = args.ppr_select
         summary.update({"batch_size": args.batch_size, "ppr_topk": args.ppr_topk,
+                        "batch_slice": args.batch_slice,
                         "ppr_build_mean": float(np.mean(builds)),
                         "records": records})
     print(json.dumps(summary), flush=True)
