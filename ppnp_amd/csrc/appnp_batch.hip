@@ -358,8 +358,6 @@ __global__ __launch_bounds__(kBlock) void k_batch_sort(BatchArgs a) {
   }
 }
 
-inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 inline int64_t bitmap_words(int64_t cols) { return (cols + 31) / 32; }
 
 // words of the workspace parts, in their order
@@ -379,17 +377,6 @@ inline void place(BatchArgs& a, void* ws, int64_t nnz_cap) {
   a.cursor = a.rowcnt + a.b;
   a.tkey = reinterpret_cast<int32_t*>(a.cursor + cursor_words(a.cols, nnz_cap));
   a.trow = a.tkey + nnz_cap;
-}
-
-inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
-
-template <typename Launch>
-inline int timed_launch(hipStream_t s, Launch launch) {
-  ktimer_begin(s);
-  launch();
-  const int rc = launch_err();
-  ktimer_mark(s, APPNP_KT_COPY);
-  return rc;
 }
 
 inline bool bad_shape(int64_t rows, int64_t cols, int64_t b) {
@@ -439,7 +426,7 @@ extern "C" int appnp_csr_batch_count(const int32_t* indptr, const int32_t* indic
   const hipError_t me = hipMemsetAsync(ws, 0, head_words(cols) * sizeof(uint32_t), s);
   ktimer_mark(s, APPNP_KT_COPY);
   if (me != hipSuccess) return APPNP_EDEVICE;
-  int rc = timed_launch(s, [&] {
+  int rc = timed_launch(s, APPNP_KT_COPY, [&] {
     if (a.words <= kMarkLdsWords) {
       const int64_t per_block = (int64_t)kWavesPerBlock * kMarkRows;
       const dim3 lds_grid((unsigned)((b + per_block - 1) / per_block));
@@ -449,9 +436,10 @@ extern "C" int appnp_csr_batch_count(const int32_t* indptr, const int32_t* indic
     }
   });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_batch_rows, grid, block, 0, s, a); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_batch_rows, grid, block, 0, s, a); });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] {
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
       hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(kScanThreads), 0, s, a);
     });
   return rc;
@@ -499,18 +487,22 @@ extern "C" int appnp_csr_batch_emit(const int32_t* indptr, const int32_t* indice
   const dim3 block(kBlock), grid(grid_rows(b));
   const dim3 word_grid((unsigned)((a.words + kBlock - 1) / kBlock));
 
-  int rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_batch_sel, word_grid, block, 0, s, a); });
+  int rc = timed_launch(s, APPNP_KT_COPY,
+                        [&] { hipLaunchKernelGGL(k_batch_sel, word_grid, block, 0, s, a); });
   if (nnz_out == 0 || rc != APPNP_OK) return rc;  // t_indptr = {0}: nothing was selected
-  rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_batch_emit, grid, block, 0, s, a); });
+  rc = timed_launch(s, APPNP_KT_COPY,
+                    [&] { hipLaunchKernelGGL(k_batch_emit, grid, block, 0, s, a); });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] {
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
       hipLaunchKernelGGL(k_batch_tscan, dim3(1), dim3(kScanThreads), 0, s, a);
     });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_batch_scatter, grid, block, 0, s, a); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_batch_scatter, grid, block, 0, s, a); });
   if (rc == APPNP_OK) {
     const dim3 seg_grid((unsigned)((n_sel + kSegsPerBlock - 1) / kSegsPerBlock));
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_batch_sort, seg_grid, block, 0, s, a); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_batch_sort, seg_grid, block, 0, s, a); });
   }
   return rc;
 }

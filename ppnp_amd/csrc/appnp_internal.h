@@ -132,6 +132,20 @@ int tuning_env(const char* name, int dflt);
 void ktimer_begin(hipStream_t s);
 void ktimer_mark(hipStream_t s, int kind);
 
+inline size_t round_up(size_t x, size_t al) { return (x + al - 1) / al * al; }
+
+inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
+
+// One launch of the top-k, push and batch entry points, bracketed for the per-launch timer.
+template <typename Launch>
+inline int timed_launch(hipStream_t s, int kind, Launch launch) {
+  ktimer_begin(s);
+  launch();
+  const int rc = launch_err();
+  ktimer_mark(s, kind);
+  return rc;
+}
+
 // Leading dimension of the internal ping-pong buffers.  A random row gather costs 128-B line
 // requests, not bytes, so rows are padded to start on a line
 // (next power of two up to one line, then whole lines) -- but only when that lowers the

@@ -32,7 +32,7 @@
 #include <algorithm>
 
 #include "appnp_internal.h"
-#include "appnp_topk_key.h"  // order_key
+#include "appnp_topk_key.h"  // order_key, digit_search
 #include "../../include/ppnp_amd.h"
 
 namespace appnp {
@@ -143,28 +143,11 @@ __global__ __launch_bounds__(kBlock) void k_topk_pick(TopkArgs a, int pass) {
   const int64_t c = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   if (c >= a.b) return;  // whole wave
   const uint32_t* h = a.hist + ((int64_t)pass * a.b + c) * kBins + 4 * lane;
-  const uint32_t h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
-  const uint32_t own = h0 + h1 + h2 + h3;
-  uint32_t suf = own;  // inclusive suffix sum over lanes >= lane
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const uint32_t t = __shfl_down(suf, off, kWave);
-    if (lane + off < kWave) suf += t;
-  }
   const uint32_t want = pass ? a.state[2 * c + 1] : (uint32_t)a.k;
   const uint32_t prefix = pass ? a.state[2 * c] : 0u;
-  uint32_t above = suf - own;  // keys in the bins of higher lanes
-  if (above < want && want <= suf) {  // exactly one lane
-    uint32_t d = 3;  // the lane's bins from the top: the first whose running count reaches want
-    if (above + h3 < want) {
-      above += h3; d = 2;
-      if (above + h2 < want) {
-        above += h2; d = 1;
-        if (above + h1 < want) { above += h1; d = 0; }
-      }
-    }
-    const int shift = 24 - 8 * pass;
-    a.state[2 * c] = prefix | ((uint32_t)(4 * lane + d) << shift);
+  uint32_t digit, above, in;
+  if (digit_search(h[0], h[1], h[2], h[3], want, lane, digit, above, in)) {  // exactly one lane
+    a.state[2 * c] = prefix | (digit << (24 - 8 * pass));
     a.state[2 * c + 1] = want - above;
   }
 }
@@ -244,23 +227,10 @@ __global__ __launch_bounds__(kBlock) void k_topk_emit(TopkArgs a) {
 
 inline int64_t sub_blocks(int64_t n) { return (n + kSubRows - 1) / kSubRows; }
 
-inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // words of the three workspace parts
 inline size_t hist_words(int64_t b) { return (size_t)4 * (size_t)b * kBins; }
 inline size_t state_words(int64_t b) { return (size_t)2 * (size_t)b; }
 inline size_t cnt_words(int64_t n, int64_t b) { return (size_t)2 * (size_t)sub_blocks(n) * (size_t)b; }
-
-inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
-
-template <typename Launch>
-inline int timed_launch(hipStream_t s, Launch launch) {
-  ktimer_begin(s);
-  launch();
-  const int rc = launch_err();
-  ktimer_mark(s, APPNP_KT_COPY);
-  return rc;
-}
 
 }  // namespace
 }  // namespace appnp
@@ -313,18 +283,21 @@ extern "C" int appnp_topk_columns(const float* X, int64_t ld_x, int64_t n, int64
   if (me != hipSuccess) return APPNP_EDEVICE;
   int rc = APPNP_OK;
   for (int pass = 0; pass < 4 && rc == APPNP_OK; ++pass) {
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_topk_hist, grid, block, 0, s, a, pass); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_topk_hist, grid, block, 0, s, a, pass); });
     if (rc == APPNP_OK)
-      rc = timed_launch(s,
+      rc = timed_launch(s, APPNP_KT_COPY,
                         [&] { hipLaunchKernelGGL(k_topk_pick, pick_grid, block, 0, s, a, pass); });
   }
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_topk_count, grid, block, 0, s, a); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_topk_count, grid, block, 0, s, a); });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] {
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
       hipLaunchKernelGGL(k_topk_scan, dim3((unsigned)a.tiles), dim3(kScanThreads), 0, s, a);
     });
   if (rc == APPNP_OK)
-    rc = timed_launch(s, [&] { hipLaunchKernelGGL(k_topk_emit, grid, block, 0, s, a); });
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_topk_emit, grid, block, 0, s, a); });
   return rc;
 }

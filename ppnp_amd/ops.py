@@ -235,6 +235,19 @@ def solve(graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
 # ---- sparse top-k PPR rows: the column selection (appnp_topk_columns) ----------------------
 
 
+def _scales(row_scale, col_scale, n: int, b: int, device):
+    """The selection's ``[row_scale, col_scale]`` (fp32 [n] / [b] on ``device``, or None), checked
+    and contiguous."""
+    scales = []
+    for name, t, m in (("row_scale", row_scale, n), ("col_scale", col_scale, b)):
+        if t is not None:
+            if t.dtype != torch.float32 or t.device != device or tuple(t.shape) != (m,):
+                raise ValueError(f"{name} must be float32 [{m}] on {device}")
+            t = t.contiguous()
+        scales.append(t)
+    return scales
+
+
 def topk_columns(X: torch.Tensor, k: int, row_scale: torch.Tensor | None = None,
                  col_scale: torch.Tensor | None = None):
     """The k largest entries of every column of X [n, b] (fp32, unit column stride, a padded
@@ -253,13 +266,7 @@ def topk_columns(X: torch.Tensor, k: int, row_scale: torch.Tensor | None = None,
     k = int(k)
     if k < 1 or (n * b > 0 and k > n):
         raise ValueError(f"k must be in [1, {n}], got {k}")
-    scales = []
-    for name, t, m in (("row_scale", row_scale, n), ("col_scale", col_scale, b)):
-        if t is not None:
-            if t.dtype != torch.float32 or t.device != X.device or tuple(t.shape) != (m,):
-                raise ValueError(f"{name} must be float32 [{m}] on {X.device}")
-            t = t.contiguous()
-        scales.append(t)
+    scales = _scales(row_scale, col_scale, n, b, X.device)
     idx = torch.empty(b, k, dtype=torch.int32, device=X.device)
     val = torch.empty(b, k, dtype=torch.float32, device=X.device)
     lib = _lib.load()
@@ -275,6 +282,22 @@ def topk_columns(X: torch.Tensor, k: int, row_scale: torch.Tensor | None = None,
 # ---- PPR columns by local forward push (appnp_push_columns) --------------------------------
 
 
+def _push_graph(fn: str, graph: Graph, rc: int | None = None):
+    """What ``fn`` (push_columns / push_topk) asks of its graph.  Before the call (``rc`` None):
+    undirected and not row-partitioned.  After it, with the call's return code: 'rw' without the
+    transpose in words, anything else through ``_lib.check``."""
+    if rc is None:
+        if not graph.symmetric:
+            raise ValueError(f"{fn} needs an undirected graph (symmetric A)")
+        if graph.row_lo != 0 or graph.row_hi != graph.n:
+            raise ValueError(f"{fn} needs a full (not row-partitioned) graph")
+        return
+    if rc == _lib.APPNP_ENOTSUP and graph.mode == "rw":
+        raise ValueError(f"{fn} on an 'rw' graph walks A_hat^T: build the graph with "
+                         "transpose=True (Graph.from_scipy(..., transpose=True))")
+    _lib.check(f"appnp_{fn}", rc)
+
+
 def push_columns(graph: Graph, idx, alpha: float = 0.1, eps: float = 1e-4,
                  max_rounds: int = 1000, out: torch.Tensor | None = None):
     """Pi[:, idx] by forward push via ``appnp_push_columns``: ``(X fp32 [n, B], rounds int32 [B],
@@ -287,10 +310,7 @@ def push_columns(graph: Graph, idx, alpha: float = 0.1, eps: float = 1e-4,
     leading dimension is passed through, the padding is not touched).  Undirected full graphs;
     'rw' needs the transpose (``Graph.from_scipy(..., transpose=True)``).  Stream-ordered on the
     current stream, no host synchronisation; see include/ppnp_amd.h."""
-    if not graph.symmetric:
-        raise ValueError("push_columns needs an undirected graph (symmetric A)")
-    if graph.row_lo != 0 or graph.row_hi != graph.n:
-        raise ValueError("push_columns needs a full (not row-partitioned) graph")
+    _push_graph("push_columns", graph)
     idx = torch.as_tensor(idx, device=graph.device).long().contiguous().reshape(-1)
     n, b = graph.n, int(idx.numel())
     X = torch.empty(n, b, dtype=torch.float32, device=graph.device) if out is None else out
@@ -307,10 +327,7 @@ def push_columns(graph: Graph, idx, alpha: float = 0.1, eps: float = 1e-4,
         rc = lib.appnp_push_columns(graph.handle, _vp(idx), b, float(alpha), float(eps),
                                     int(max_rounds), _vp(X), max(_ld(X), b), _vp(rounds),
                                     _vp(left), _vp(ws), ws_bytes, _stream(graph.device))
-    if rc == _lib.APPNP_ENOTSUP and graph.mode == "rw":
-        raise ValueError("push_columns on an 'rw' graph walks A_hat^T: build the graph with "
-                         "transpose=True (Graph.from_scipy(..., transpose=True))")
-    _lib.check("appnp_push_columns", rc)
+    _push_graph("push_columns", graph, rc)
     return X, rounds, left
 
 
@@ -343,10 +360,7 @@ def push_topk(graph: Graph, idx, k: int, alpha: float = 0.1, eps: float = 1e-4,
     the workspace (36 n bytes per slot); None picks ``push_topk_slots``.  One call takes any
     number of sources.  ``rounds`` / ``left`` and the graph requirements are ``push_columns``'s.
     Stream-ordered on the current stream, no host synchronisation; see include/ppnp_amd.h."""
-    if not graph.symmetric:
-        raise ValueError("push_topk needs an undirected graph (symmetric A)")
-    if graph.row_lo != 0 or graph.row_hi != graph.n:
-        raise ValueError("push_topk needs a full (not row-partitioned) graph")
+    _push_graph("push_topk", graph)
     idx = torch.as_tensor(idx, device=graph.device).long().contiguous().reshape(-1)
     n, b = graph.n, int(idx.numel())
     k = int(k)
@@ -354,13 +368,7 @@ def push_topk(graph: Graph, idx, k: int, alpha: float = 0.1, eps: float = 1e-4,
         raise ValueError(f"k must be in [1, {n}], got {k}")
     if k > PUSH_TOPK_MAX_K:
         raise ValueError(f"push_topk selects at most k = {PUSH_TOPK_MAX_K}, got {k}")
-    scales = []
-    for name, t, m in (("row_scale", row_scale, n), ("col_scale", col_scale, b)):
-        if t is not None:
-            if t.dtype != torch.float32 or t.device != graph.device or tuple(t.shape) != (m,):
-                raise ValueError(f"{name} must be float32 [{m}] on {graph.device}")
-            t = t.contiguous()
-        scales.append(t)
+    scales = _scales(row_scale, col_scale, n, b, graph.device)
     if slots is None:
         slots = push_topk_slots(graph, b) if n * b > 0 else 1
     slots = int(slots)
@@ -378,10 +386,7 @@ def push_topk(graph: Graph, idx, k: int, alpha: float = 0.1, eps: float = 1e-4,
                                  int(max_rounds), k, _vp(scales[0]), _vp(scales[1]),
                                  _vp(out_idx), _vp(out_val), k, _vp(rounds), _vp(left), slots,
                                  _vp(ws), ws_bytes, _stream(graph.device))
-    if rc == _lib.APPNP_ENOTSUP and graph.mode == "rw":
-        raise ValueError("push_topk on an 'rw' graph walks A_hat^T: build the graph with "
-                         "transpose=True (Graph.from_scipy(..., transpose=True))")
-    _lib.check("appnp_push_topk", rc)
+    _push_graph("push_topk", graph, rc)
     return out_idx, out_val, rounds, left
 
 

@@ -205,6 +205,29 @@ class SparsePPR(SparseFeatures):
         return sub, sel
 
 
+def _selected(graph: Graph, idx: torch.Tensor, k: int, K, alpha, tol, chunk, eps, max_rounds, info,
+              lists: bool, rs=None, cs=None):
+    """The flat ``(indices int32, values fp32)`` of the k selected entries of every source in
+    ``idx``, source after source: ONE ``push_topk`` call (``lists``), or ``ppr_columns`` +
+    ``topk_columns`` for ``chunk`` sources at a time.  ``rs`` [N] / ``cs`` [len(idx)]: the
+    selection's row and column scales."""
+    if not idx.numel():
+        empty_i = torch.empty(0, dtype=torch.int32, device=graph.device)
+        return empty_i, empty_i.float()
+    if lists:
+        i, v, rounds, left = push_topk(graph, idx, k, alpha, eps, max_rounds, rs, cs)
+        if info is not None:
+            info.append((rounds, left))
+        return i.reshape(-1), v.reshape(-1)
+    ix, dv = [], []
+    for s in range(0, int(idx.numel()), int(chunk)):
+        cols = ppr_columns(graph, idx[s:s + chunk], K, alpha, tol, eps, max_rounds, info)
+        i, v = topk_columns(cols, k, rs, None if cs is None else cs[s:s + chunk])
+        ix.append(i.reshape(-1))
+        dv.append(v.reshape(-1))
+    return torch.cat(ix), torch.cat(dv)
+
+
 def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
               tol: float | None = None, chunk: int = 128, eps: float | None = None,
               max_rounds: int = 1000, info: list | None = None,
@@ -231,24 +254,11 @@ def topk_rows(graph: Graph, idx, k: int, K: int = 10, alpha: float = 0.1,
         _, _, _, dinv = graph.csr()  # fp64 1 / D
         rs = (1.0 / dinv).float()
         cs_all = dinv[idx].float()
-    ix, dv = [], []
-    if lists and idx.numel():
-        i, v, rounds, left = push_topk(graph, idx, k, alpha, eps, max_rounds, rs, cs_all)
-        if info is not None:
-            info.append((rounds, left))
-        ix.append(i.reshape(-1))
-        dv.append(v.reshape(-1))
-    for s in ([] if lists else range(0, int(idx.numel()), int(chunk))):
-        part = idx[s:s + chunk]
-        cols = ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info)
-        i, v = topk_columns(cols, k, rs, None if cs_all is None else cs_all[s:s + chunk])
-        ix.append(i.reshape(-1))
-        dv.append(v.reshape(-1))
+    ix, dv = _selected(graph, idx, k, K, alpha, tol, chunk, eps, max_rounds, info, lists, rs,
+                       cs_all)
     B = int(idx.numel())
     indptr = torch.arange(B + 1, dtype=torch.int64, device=graph.device) * int(k)
-    empty_i = torch.empty(0, dtype=torch.int32, device=graph.device)
-    return SparsePPR(indptr, torch.cat(ix) if ix else empty_i,
-                     torch.cat(dv) if dv else empty_i.float(), (B, graph.n), device=graph.device)
+    return SparsePPR(indptr, ix, dv, (B, graph.n), device=graph.device)
 
 
 def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
@@ -280,21 +290,10 @@ def sparsified_ppr(graph: Graph, k: int, K: int = 10, alpha: float = 0.1,
     n = graph.n
     if n * int(k) >= 2**31:
         raise ValueError("sparsified_ppr: N * k exceeds the int32 CSR index range")
-    ix, dv = [], []
-    if lists:
-        i, v, rounds, left = push_topk(graph, torch.arange(n, device=graph.device), k, alpha,
-                                       eps, max_rounds)
-        if info is not None:
-            info.append((rounds, left))
-        ix.append(i.reshape(-1))
-        dv.append(v.reshape(-1))
-    for s in ([] if lists else range(0, n, int(chunk))):
-        part = torch.arange(s, min(n, s + chunk), device=graph.device)
-        i, v = topk_columns(ppr_columns(graph, part, K, alpha, tol, eps, max_rounds, info), k)
-        ix.append(i.reshape(-1))
-        dv.append(v.reshape(-1))
+    ix, dv = _selected(graph, torch.arange(n, device=graph.device), k, K, alpha, tol, chunk, eps,
+                       max_rounds, info, lists)
     indptr = torch.arange(n + 1, dtype=torch.int64, device=graph.device) * int(k)
-    csc = SparsePPR(indptr, torch.cat(ix), torch.cat(dv), (n, n), device=graph.device)
+    csc = SparsePPR(indptr, ix, dv, (n, n), device=graph.device)
     ip, jx, val = csc.transpose()
     P = SparsePPR(ip, jx, val, (n, n), device=graph.device)
     P._t = (csc.indptr, csc.indices, csc.data)  # the CSC is P^T: the backward's operand
