@@ -647,15 +647,21 @@ int graph_build_source_blocks(appnp_graph* g, int lpe, const int32_t* a_indptr,
   const int64_t rg = std::max<int64_t>(1, (rows + passes * slots - 1) / (passes * slots));
   const int64_t cells = passes * nb * slots;
   if (cells + 1 > INT32_MAX) return APPNP_ERANGE;
-  int rc = APPNP_OK;
-  int32_t* cnt = nullptr;
-  int64_t *bsum = nullptr, *tot = nullptr;
-  auto ok = [&](hipError_t e) {
-    if (e != hipSuccess && rc == APPNP_OK)
-      rc = (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) ? APPNP_ENOMEM
-                                                                       : APPNP_EDEVICE;
-    return rc == APPNP_OK;
-  };
+  // From here a failure leaves the graph without the copy, and usable: the copy is released, and
+  // the failed call's error is cleared from this thread's last-error slot, or the next
+  // hipGetLastError (a launch check here or in the caller's framework) would report it as its
+  // own
+  struct Undo {
+    appnp_graph* g;
+    ~Undo() {
+      if (!g) return;
+      (void)hipGetLastError();
+      graph_free_source_blocks(g);
+    }
+  } undo{g};
+  DeviceScratch tmp;  // declared after undo: freed before it runs
+  int32_t* cnt;
+  int64_t *bsum, *tot;
   // a unit graph (every entry of A+I is 1) stores no values: A_hat_ij = dl_i dr_j.
   // APPNP_REM_VF=0 keeps the values (tuning override)
   const bool vf = g->unit && tuning_env("APPNP_REM_VF", 1) != 0;
@@ -663,91 +669,65 @@ int graph_build_source_blocks(appnp_graph* g, int lpe, const int32_t* a_indptr,
   const unsigned grid = (unsigned)((n_groups + kWalkWaves - 1) / kWalkWaves);
   const size_t lds = (size_t)kWalkWaves * nb * sizeof(int32_t);
   int64_t h_tot[2] = {0, 0};  // padded entries, near entries
-  if (ok(hipMalloc(&g->rb_off, (cells + 1) * sizeof(int32_t))) &&
-      ok(hipMalloc(&cnt, cells * sizeof(int32_t))) &&
-      ok(hipMalloc(&bsum, scan_partials(cells) * sizeof(int64_t))) &&
-      ok(hipMalloc(&tot, 2 * sizeof(int64_t))) &&
-      ok(hipMemsetAsync(tot, 0, 2 * sizeof(int64_t), s))) {
-    hipLaunchKernelGGL(k_rb_walk<false>, dim3(grid), dim3(kBlock), lds, s, g->row_ptr, g->col,
-                       g->val, rows, g->row_lo, (int)rg, (int)nb, br_log2, chunk, n_groups, cnt,
-                       nullptr, nullptr, nullptr,
-                       reinterpret_cast<unsigned long long*>(tot + 1));
-    if (partial && a_nnz > 0 && ok(hipGetLastError()) &&
-        ok(hipMemsetAsync(tot + 1, 0, sizeof(int64_t), s))) {
-      // the near count of the WHOLE A (replacing the held rows' count of the walk)
-      const int64_t nblk = std::min<int64_t>((g->n + kBlock - 1) / kBlock, 4096);
-      hipLaunchKernelGGL(k_near_all, dim3((unsigned)std::max<int64_t>(1, nblk)), dim3(kBlock), 0,
-                         s, a_indptr, a_indices, g->n,
-                         reinterpret_cast<unsigned long long*>(tot + 1));
-    }
-    if (ok(hipGetLastError()) && ok(exclusive_scan(cnt, cells, g->rb_off, bsum, tot, s)) &&
-        ok(hipMemcpyAsync(h_tot, tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s)) &&
-        ok(hipStreamSynchronize(s))) {
-      // padded total: the int32 segment offsets must hold it
-      if (h_tot[0] > INT32_MAX) rc = APPNP_ERANGE;
-    }
-    const int64_t total = std::max<int64_t>(1, h_tot[0]);
+  APPNP_TRY(device_alloc(&g->rb_off, cells + 1));
+  APPNP_TRY(tmp.get(&cnt, cells));
+  APPNP_TRY(tmp.get(&bsum, scan_partials(cells)));
+  APPNP_TRY(tmp.get(&tot, 2));
+  APPNP_TRY(hipMemsetAsync(tot, 0, 2 * sizeof(int64_t), s));
+  hipLaunchKernelGGL(k_rb_walk<false>, dim3(grid), dim3(kBlock), lds, s, g->row_ptr, g->col,
+                     g->val, rows, g->row_lo, (int)rg, (int)nb, br_log2, chunk, n_groups, cnt,
+                     nullptr, nullptr, nullptr, reinterpret_cast<unsigned long long*>(tot + 1));
+  if (partial && a_nnz > 0) {
+    // the near count of the WHOLE A (replacing the held rows' count of the walk)
+    APPNP_TRY(hipGetLastError());
+    APPNP_TRY(hipMemsetAsync(tot + 1, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL(k_near_all, dim3(std::min(blocks_for(g->n), 4096u)), dim3(kBlock), 0, s,
+                       a_indptr, a_indices, g->n, reinterpret_cast<unsigned long long*>(tot + 1));
+  }
+  APPNP_TRY(hipGetLastError());
+  APPNP_TRY(exclusive_scan(cnt, cells, g->rb_off, bsum, tot, s));
+  APPNP_TRY(hipMemcpyAsync(h_tot, tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
+  // padded total: the int32 segment offsets must hold it
+  if (h_tot[0] > INT32_MAX) return APPNP_ERANGE;
+  const int64_t total = std::max<int64_t>(1, h_tot[0]);
 #ifdef APPNP_TESTING
-    // APPNP_SB_TEST_OOM (test library): ask for an impossible size, so the best-effort ENOMEM
-    // path runs with a real failing hipMalloc
-    const size_t ent_bytes = test_env("APPNP_SB_TEST_OOM", 0) ? (size_t)1 << 60
-                                                              : (size_t)total * sizeof(uint32_t);
+  // APPNP_SB_TEST_OOM (test library): ask for an impossible size, so the best-effort ENOMEM
+  // path runs with a real failing hipMalloc
+  const int64_t ent_count = test_env("APPNP_SB_TEST_OOM", 0) ? (int64_t)1 << 58 : total;
 #else
-    const size_t ent_bytes = (size_t)total * sizeof(uint32_t);
+  const int64_t ent_count = total;
 #endif
-    if (rc == APPNP_OK && ok(hipMalloc(&g->rb_ent, ent_bytes)) &&
-        (vf || ok(hipMalloc(&g->rb_val, total * sizeof(float)))) &&
-        ok(hipMemsetAsync(g->rb_ent, 0xff, total * sizeof(uint32_t), s)) &&  // kRemNone
-        (vf || ok(hipMemsetAsync(g->rb_val, 0, total * sizeof(float), s))) &&
-        (!vf || ok(hipMalloc(&g->rb_dl, std::max<int64_t>(1, rows) * sizeof(float)))) &&
-        (!vf || g->mode != APPNP_NORM_SYM ||
-         ok(hipMalloc(&g->rb_dr, std::max<int64_t>(1, g->n) * sizeof(float)))) &&
-        ok(hipMalloc(&g->rb_cblk, std::max<int64_t>(1, total / chunk) * sizeof(int32_t)))) {
-      hipLaunchKernelGGL(k_rb_walk<true>, dim3(grid), dim3(kBlock), lds, s, g->row_ptr, g->col,
-                         g->val, rows, g->row_lo, (int)rg, (int)nb, br_log2, chunk, n_groups,
-                         nullptr,
-                         g->rb_off,
-                         g->rb_ent, g->rb_val, nullptr);
-      if (vf && ok(hipGetLastError())) {
-        // dl: the held rows' scale (local index); dr: every column's (global index)
-        if (rows > 0)
-          hipLaunchKernelGGL(k_dinv_f32, dim3((unsigned)((rows + kBlock - 1) / kBlock)),
-                             dim3(kBlock), 0, s, g->dinv + g->row_lo, rows, g->rb_dl);
-        if (g->rb_dr && g->n > 0)
-          hipLaunchKernelGGL(k_dinv_f32, dim3((unsigned)((g->n + kBlock - 1) / kBlock)),
-                             dim3(kBlock), 0, s, g->dinv, g->n, g->rb_dr);
-      }
-      if (ok(hipGetLastError()))
-        hipLaunchKernelGGL(k_rb_chunks, dim3((unsigned)((cells + kBlock - 1) / kBlock)),
-                           dim3(kBlock), 0, s, g->rb_off, cells, (int)nb, chunk, g->rb_cblk);
-      // near entries per entry of A_hat: the held rows' (full graph) or the whole graph's
-      // (row partition: A's off-diagonal entries + the n diagonal ones)
-      const double denom = partial ? (double)(a_nnz + g->n) : (double)g->nnz_hat;
-      if (ok(hipGetLastError()) && ok(hipStreamSynchronize(s)))
-        g->near_frac = denom > 0 ? (double)h_tot[1] / denom : 0.0;
-    }
+  APPNP_TRY(device_alloc(&g->rb_ent, ent_count));
+  if (!vf) APPNP_TRY(device_alloc(&g->rb_val, total));
+  APPNP_TRY(hipMemsetAsync(g->rb_ent, 0xff, total * sizeof(uint32_t), s));  // kRemNone
+  if (!vf) APPNP_TRY(hipMemsetAsync(g->rb_val, 0, total * sizeof(float), s));
+  // dl: the held rows' scale (local index); dr: every column's (global index)
+  if (vf) APPNP_TRY(device_alloc(&g->rb_dl, rows));
+  if (vf && g->mode == APPNP_NORM_SYM) APPNP_TRY(device_alloc(&g->rb_dr, g->n));
+  APPNP_TRY(device_alloc(&g->rb_cblk, total / chunk));
+  hipLaunchKernelGGL(k_rb_walk<true>, dim3(grid), dim3(kBlock), lds, s, g->row_ptr, g->col,
+                     g->val, rows, g->row_lo, (int)rg, (int)nb, br_log2, chunk, n_groups, nullptr,
+                     g->rb_off, g->rb_ent, g->rb_val, nullptr);
+  if (vf) {
+    APPNP_TRY(hipGetLastError());
+    if (rows > 0)
+      hipLaunchKernelGGL(k_dinv_f32, dim3(blocks_for(rows)), dim3(kBlock), 0, s,
+                         g->dinv + g->row_lo, rows, g->rb_dl);
+    if (g->rb_dr && g->n > 0)
+      hipLaunchKernelGGL(k_dinv_f32, dim3(blocks_for(g->n)), dim3(kBlock), 0, s, g->dinv, g->n,
+                         g->rb_dr);
   }
-  if (cnt) (void)hipFree(cnt);
-  if (bsum) (void)hipFree(bsum);
-  if (tot) (void)hipFree(tot);
-  if (rc != APPNP_OK) {
-    // the graph stays usable without the copy: clear the failed call's error from this
-    // thread's last-error slot, or the next hipGetLastError (a launch check here or in the
-    // caller's framework) would report it as its own
-    (void)hipGetLastError();
-    if (g->rb_off) (void)hipFree(g->rb_off);
-    if (g->rb_ent) (void)hipFree(g->rb_ent);
-    if (g->rb_val) (void)hipFree(g->rb_val);
-    if (g->rb_cblk) (void)hipFree(g->rb_cblk);
-    if (g->rb_dl) (void)hipFree(g->rb_dl);
-    if (g->rb_dr) (void)hipFree(g->rb_dr);
-    g->rb_dl = g->rb_dr = nullptr;
-    g->rb_off = nullptr;
-    g->rb_ent = nullptr;
-    g->rb_val = nullptr;
-    g->rb_cblk = nullptr;
-    return rc;
-  }
+  APPNP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_rb_chunks, dim3(blocks_for(cells)), dim3(kBlock), 0, s, g->rb_off, cells,
+                     (int)nb, chunk, g->rb_cblk);
+  APPNP_TRY(hipGetLastError());
+  APPNP_TRY(hipStreamSynchronize(s));
+  // near entries per entry of A_hat: the held rows' (full graph) or the whole graph's
+  // (row partition: A's off-diagonal entries + the n diagonal ones)
+  const double denom = partial ? (double)(a_nnz + g->n) : (double)g->nnz_hat;
+  g->near_frac = denom > 0 ? (double)h_tot[1] / denom : 0.0;
+  undo.g = nullptr;  // built: the graph keeps the copy
   g->rb_total = h_tot[0];
   g->rb_nb = (int32_t)nb;
   g->rb_br_log2 = br_log2;

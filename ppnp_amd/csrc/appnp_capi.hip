@@ -100,15 +100,8 @@ namespace {
 
 using appnp::ktimer_begin;
 using appnp::ktimer_mark;
-
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline int dev_err(hipError_t e) {
-  if (e == hipSuccess) return APPNP_OK;
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) return APPNP_ENOMEM;
-  if (e == hipErrorInvalidValue) return APPNP_EINVAL;
-  return APPNP_EDEVICE;
-}
+using appnp::as_stream;
+using appnp::dev_err;
 
 // One launch (or copy) on `s` between the kernel timer's two events, tagged `kind` (APPNP_KT_*).
 // Every launch of this unit's propagation entry points goes through here.

@@ -58,18 +58,11 @@ struct appnp_dist {
 
 namespace {
 
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline int dev_err(hipError_t e) {
-  if (e == hipSuccess) return APPNP_OK;
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) return APPNP_ENOMEM;
-  if (e == hipErrorInvalidValue) return APPNP_EINVAL;
-  return APPNP_EDEVICE;
-}
+using appnp::as_stream;
+using appnp::dev_err;
+using appnp::round_up;
 
 constexpr size_t kAlign = 256;
-
-inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 struct WsLayout {
   int64_t ld = 0;          // elements per row of the iterate buffers
@@ -91,16 +84,17 @@ WsLayout ws_layout(const appnp_dist* d, int64_t f, int dtype) {
   const int64_t es = dtype == APPNP_F32 ? 4 : 2;
   const size_t rows_pad = (size_t)(d->shard * d->nranks);
   w.ld = appnp::line_ld(f, dtype);
-  w.buf_bytes = align_up(rows_pad * (size_t)(w.ld * es));
+  w.buf_bytes = round_up(rows_pad * (size_t)(w.ld * es), kAlign);
   w.partial_off = 2 * w.buf_bytes;
-  const size_t partial = d->overlap ? align_up((size_t)d->shard * (size_t)w.ld * 4) : 0;
+  const size_t partial = d->overlap ? round_up((size_t)d->shard * (size_t)w.ld * 4, kAlign) : 0;
   w.total = w.partial_off + partial;
   if (dtype == APPNP_F32 && appnp_split_layout(d->g, f, &w.fs, &w.rw) == APPNP_OK) {
-    w.main_bytes = align_up(rows_pad * (size_t)w.fs * 4);
-    w.part_bytes = w.main_bytes + align_up(rows_pad * (size_t)w.rw * 4);
+    w.main_bytes = round_up(rows_pad * (size_t)w.fs * 4, kAlign);
+    w.part_bytes = w.main_bytes + round_up(rows_pad * (size_t)w.rw * 4, kAlign);
     w.f4 = (f + 3) / 4 * 4;
-    w.stage_off = 2 * w.part_bytes + (d->overlap ? align_up((size_t)d->shard * w.fs * 4) : 0);
-    w.stage_bytes = align_up((size_t)d->shard * (size_t)w.f4 * 4);
+    w.stage_off =
+        2 * w.part_bytes + (d->overlap ? round_up((size_t)d->shard * w.fs * 4, kAlign) : 0);
+    w.stage_bytes = round_up((size_t)d->shard * (size_t)w.f4 * 4, kAlign);
     w.split_total = w.stage_off + 2 * w.stage_bytes;
   }
   return w;
@@ -272,8 +266,13 @@ int propagate_split_rows(appnp_dist* d, const WsLayout& w, const float* H, int64
   return rc;
 }
 
+// rows x (f elements) between two row-major matrices with leading dimensions in elements
 hipError_t copy_rows(void* dst, int64_t ld_dst, const void* src, int64_t ld_src, int64_t rows,
-                     int64_t f, int64_t es, hipStream_t s);
+                     int64_t f, int64_t es, hipStream_t s) {
+  if (rows <= 0 || f <= 0) return hipSuccess;
+  return hipMemcpy2DAsync(dst, (size_t)(ld_dst * es), src, (size_t)(ld_src * es),
+                          (size_t)(f * es), (size_t)rows, hipMemcpyDeviceToDevice, s);
+}
 
 // appnp_dist_propagate on the split layout with the pipelined exchange: the remainder part is
 // all-gathered first on xs, the main part by one broadcast per shard; the main product runs FIRST
@@ -364,14 +363,6 @@ int propagate_rows_pipelined(appnp_dist* d, const WsLayout& w, const void* H, in
     if (rc == APPNP_OK && !last) rc = exchange_shards(d, buf[(k + 1) & 1], shard_bytes, s);
   }
   return rc;
-}
-
-// rows x (f elements) between two row-major matrices with leading dimensions in elements
-hipError_t copy_rows(void* dst, int64_t ld_dst, const void* src, int64_t ld_src, int64_t rows,
-                     int64_t f, int64_t es, hipStream_t s) {
-  if (rows <= 0 || f <= 0) return hipSuccess;
-  return hipMemcpy2DAsync(dst, (size_t)(ld_dst * es), src, (size_t)(ld_src * es),
-                          (size_t)(f * es), (size_t)rows, hipMemcpyDeviceToDevice, s);
 }
 
 // RCCL, resolved at first use (appnp_allgather_rccl, appnp_bcast_rccl)

@@ -235,24 +235,13 @@ int64_t scan_partials(int64_t rows) {
 
 hipError_t exclusive_scan(const int32_t* cnt, int64_t rows, int32_t* out, int64_t* d_bsum,
                           int64_t* d_total, hipStream_t s) {
-  const int64_t nb = std::max<int64_t>(1, (rows + kScanTile - 1) / kScanTile);
+  const int64_t nb = scan_partials(rows);
   hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(kBlock), 0, s, cnt, rows, d_bsum);
   hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(kBlock), 0, s, d_bsum, nb, d_total);
   hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(kBlock), 0, s, cnt, rows, d_bsum,
                      d_total, out);
   return hipGetLastError();
 }
-
-namespace {
-
-template <typename T>
-hipError_t dalloc(T** p, int64_t count) {
-  *p = nullptr;
-  if (count <= 0) count = 1;
-  return hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T));
-}
-
-}  // namespace
 
 namespace {
 
@@ -278,60 +267,54 @@ int build_heavy(const int32_t* rp, int64_t rows, int32_t thr, hipStream_t s, int
   *out = nullptr;
   *n_out = 0;
   if (rows <= 0) return APPNP_OK;
-  int32_t *flag = nullptr, *pos = nullptr;
-  int64_t *bsum = nullptr, *tot = nullptr;
+  DeviceScratch tmp;
+  int32_t *flag, *pos;
+  int64_t *bsum, *tot;
   int64_t h_tot = 0;
-  int rc = APPNP_OK;
-  const unsigned grid = (unsigned)((rows + kBlock - 1) / kBlock);
-  if (hipMalloc(&flag, rows * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc(&pos, (rows + 1) * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc(&bsum, scan_partials(rows) * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc(&tot, sizeof(int64_t)) != hipSuccess) {
-    rc = APPNP_ENOMEM;
-  } else {
-    hipLaunchKernelGGL(k_heavy_flags, dim3(grid), dim3(kBlock), 0, s, rp, rows, thr, flag);
-    if (exclusive_scan(flag, rows, pos, bsum, tot, s) != hipSuccess ||
-        hipMemcpyAsync(&h_tot, tot, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      rc = APPNP_EDEVICE;
-    } else if (h_tot > 0) {
-      if (hipMalloc(out, h_tot * sizeof(int32_t)) != hipSuccess) {
-        rc = APPNP_ENOMEM;
-      } else {
-        hipLaunchKernelGGL(k_heavy_scatter, dim3(grid), dim3(kBlock), 0, s, flag, pos, rows, *out);
-        if (hipStreamSynchronize(s) != hipSuccess) rc = APPNP_EDEVICE;
-        *n_out = h_tot;
-      }
-    }
-  }
-  if (flag) (void)hipFree(flag);
-  if (pos) (void)hipFree(pos);
-  if (bsum) (void)hipFree(bsum);
-  if (tot) (void)hipFree(tot);
-  return rc;
+  APPNP_TRY(tmp.get(&flag, rows));
+  APPNP_TRY(tmp.get(&pos, rows + 1));
+  APPNP_TRY(tmp.get(&bsum, scan_partials(rows)));
+  APPNP_TRY(tmp.get(&tot, 1));
+  hipLaunchKernelGGL(k_heavy_flags, dim3(blocks_for(rows)), dim3(kBlock), 0, s, rp, rows, thr,
+                     flag);
+  APPNP_TRY(exclusive_scan(flag, rows, pos, bsum, tot, s));
+  APPNP_TRY(hipMemcpyAsync(&h_tot, tot, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
+  if (h_tot == 0) return APPNP_OK;
+  APPNP_TRY(device_alloc(out, h_tot));
+  *n_out = h_tot;
+  hipLaunchKernelGGL(k_heavy_scatter, dim3(blocks_for(rows)), dim3(kBlock), 0, s, flag, pos, rows,
+                     *out);
+  APPNP_TRY(hipStreamSynchronize(s));
+  return APPNP_OK;
+}
+
+// The source-blocked copy (graph_build_source_blocks): released here and when that builder fails.
+void graph_free_source_blocks(appnp_graph* g) {
+  void* ptrs[] = {g->rb_off, g->rb_ent, g->rb_val, g->rb_cblk, g->rb_dl, g->rb_dr};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  g->rb_off = g->rb_cblk = nullptr;
+  g->rb_ent = nullptr;
+  g->rb_val = g->rb_dl = g->rb_dr = nullptr;
+  g->rb_nb = g->rb_passes = 0;
+  g->rb_total = 0;
 }
 
 void graph_free(appnp_graph* g) {
   if (!g) return;
   void* ptrs[] = {g->row_ptr, g->col, g->val, g->lrow_ptr, g->lcol, g->lval,
                   g->rrow_ptr, g->rcol, g->rval, g->dinv, g->t_row_ptr, g->t_col, g->t_val,
-                  g->heavy, g->t_heavy, g->hub, g->t_hub, g->rb_off, g->rb_ent, g->rb_val, g->rb_cblk,
-                  g->rb_dl, g->rb_dr, g->sh_off};
+                  g->heavy, g->t_heavy, g->hub, g->t_hub, g->sh_off};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  graph_free_source_blocks(g);
   g->row_ptr = g->col = g->lrow_ptr = g->lcol = g->rrow_ptr = g->rcol = nullptr;
   g->val = g->lval = g->rval = nullptr;
   g->dinv = nullptr;
   g->t_row_ptr = g->t_col = nullptr;
   g->t_val = nullptr;
   g->heavy = g->t_heavy = g->hub = g->t_hub = nullptr;
-  g->rb_off = nullptr;
-  g->rb_ent = nullptr;
-  g->rb_val = nullptr;
-  g->rb_cblk = nullptr;
-  g->rb_dl = g->rb_dr = nullptr;
-  g->rb_nb = g->rb_passes = 0;
-  g->rb_total = 0;
   g->sh_off = nullptr;
   g->sh_n = 0;
   g->sh_rows = 0;
@@ -366,19 +349,22 @@ int graph_build_shard_offsets(appnp_graph* g, int nshards, int64_t shard_rows, h
     return APPNP_EINVAL;
   const int64_t rows = g->row_hi - g->row_lo;
   if (g->sh_off && g->sh_n == nshards && g->sh_rows == shard_rows) return APPNP_OK;
+  // the new table replaces the graph's only once it is complete: a failure keeps the old one
   int32_t* off = nullptr;
-  hipError_t e = hipMalloc(&off, std::max<int64_t>(1, (nshards + 1) * rows) * sizeof(int32_t));
-  if (e == hipSuccess && rows > 0) {
-    hipLaunchKernelGGL(k_shard_offsets, dim3((unsigned)((rows + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, g->row_ptr, g->col, rows, nshards, shard_rows, off);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    if (off) (void)hipFree(off);
+  const int rc = [&]() -> int {
+    APPNP_TRY(device_alloc(&off, (nshards + 1) * rows));
+    if (rows > 0) {
+      hipLaunchKernelGGL(k_shard_offsets, dim3(blocks_for(rows)), dim3(kBlock), 0, s, g->row_ptr,
+                         g->col, rows, nshards, shard_rows, off);
+      APPNP_TRY(hipGetLastError());
+    }
+    APPNP_TRY(hipStreamSynchronize(s));
+    return APPNP_OK;
+  }();
+  if (rc != APPNP_OK) {
+    (void)hipFree(off);
     (void)hipGetLastError();
-    return (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) ? APPNP_ENOMEM
-                                                                       : APPNP_EDEVICE;
+    return rc;
   }
   if (g->sh_off) (void)hipFree(g->sh_off);
   g->sh_off = off;
@@ -387,32 +373,19 @@ int graph_build_shard_offsets(appnp_graph* g, int nshards, int64_t shard_rows, h
   return APPNP_OK;
 }
 
-#define APPNP_TRY(expr)                                                         \
-  do {                                                                          \
-    hipError_t e_ = (expr);                                                     \
-    if (e_ != hipSuccess) {                                                     \
-      rc = (e_ == hipErrorOutOfMemory || e_ == hipErrorMemoryAllocation)        \
-               ? APPNP_ENOMEM : APPNP_EDEVICE;                                  \
-      goto done;                                                                \
-    }                                                                           \
-  } while (0)
-
+// On failure the graph holds whatever was allocated so far: the caller releases it (graph_free).
 int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t n,
                 int64_t nnz, int mode, int64_t row_lo, int64_t row_hi, int split, hipStream_t s,
                 appnp_graph* g) {
-  int rc = APPNP_OK;
   const int64_t rows = row_hi - row_lo;
-  int32_t *cnt = nullptr, *cnt_l = nullptr, *cnt_r = nullptr;
-  int64_t* bsum = nullptr;
-  int64_t* totals = nullptr;  // [3]
-  unsigned* flags = nullptr;  // [3]: err, asym, non-unit weights
+  DeviceScratch tmp;
+  int32_t *cnt, *cnt_l = nullptr, *cnt_r = nullptr;
+  int64_t* bsum;
+  int64_t* totals;  // [3]
+  unsigned* flags;  // [3]: err, asym, non-unit weights
   int64_t h_tot[3] = {0, 0, 0};
   unsigned h_flags[3] = {0, 0, 0};
-  const int64_t nb_scan = std::max<int64_t>(1, (rows + kScanTile - 1) / kScanTile);
-  const unsigned blocks_n = (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock);
-  const unsigned blocks_r = (unsigned)std::max<int64_t>(1, (rows + kBlock - 1) / kBlock);
-  RowCounts rc_ptrs{};
-  CsrOut o_all{}, o_loc{}, o_rem{};
+  (void)nnz;
 
   g->n = n;
   g->row_lo = row_lo;
@@ -420,28 +393,27 @@ int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals
   g->mode = mode;
   g->split = split ? 1 : 0;
   APPNP_TRY(hipGetDevice(&g->device));
-  APPNP_TRY(dalloc(&g->dinv, n));
-  APPNP_TRY(dalloc(&g->row_ptr, rows + 1));
-  APPNP_TRY(dalloc(&cnt, rows));
+  APPNP_TRY(device_alloc(&g->dinv, n));
+  APPNP_TRY(device_alloc(&g->row_ptr, rows + 1));
+  APPNP_TRY(tmp.get(&cnt, rows));
   if (split) {
-    APPNP_TRY(dalloc(&g->lrow_ptr, rows + 1));
-    APPNP_TRY(dalloc(&g->rrow_ptr, rows + 1));
-    APPNP_TRY(dalloc(&cnt_l, rows));
-    APPNP_TRY(dalloc(&cnt_r, rows));
+    APPNP_TRY(device_alloc(&g->lrow_ptr, rows + 1));
+    APPNP_TRY(device_alloc(&g->rrow_ptr, rows + 1));
+    APPNP_TRY(tmp.get(&cnt_l, rows));
+    APPNP_TRY(tmp.get(&cnt_r, rows));
   }
-  APPNP_TRY(dalloc(&bsum, nb_scan));
-  APPNP_TRY(dalloc(&totals, 3));
-  APPNP_TRY(dalloc(&flags, 3));
+  APPNP_TRY(tmp.get(&bsum, scan_partials(rows)));
+  APPNP_TRY(tmp.get(&totals, 3));
+  APPNP_TRY(tmp.get(&flags, 3));
   APPNP_TRY(hipMemsetAsync(flags, 0, 3 * sizeof(unsigned), s));
   APPNP_TRY(hipMemsetAsync(totals, 0, 3 * sizeof(int64_t), s));
 
-  rc_ptrs = RowCounts{cnt, cnt_l, cnt_r};
   if (n > 0) {
-    hipLaunchKernelGGL(k_degree, dim3(blocks_n), dim3(kBlock), 0, s, indptr, indices, vals, n,
-                       mode, g->dinv, row_lo, row_hi, rc_ptrs, flags);
+    hipLaunchKernelGGL(k_degree, dim3(blocks_for(n)), dim3(kBlock), 0, s, indptr, indices, vals, n,
+                       mode, g->dinv, row_lo, row_hi, RowCounts{cnt, cnt_l, cnt_r}, flags);
     APPNP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_symcheck, dim3(blocks_n), dim3(kBlock), 0, s, indptr, indices, vals, n,
-                       flags + 1);
+    hipLaunchKernelGGL(k_symcheck, dim3(blocks_for(n)), dim3(kBlock), 0, s, indptr, indices, vals,
+                       n, flags + 1);
     APPNP_TRY(hipGetLastError());
   }
   APPNP_TRY(exclusive_scan(cnt, rows, g->row_ptr, bsum, totals + 0, s));
@@ -452,51 +424,34 @@ int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals
   APPNP_TRY(hipMemcpyAsync(h_tot, totals, sizeof(h_tot), hipMemcpyDeviceToHost, s));
   APPNP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s));
   APPNP_TRY(hipStreamSynchronize(s));
-  if (h_flags[0]) {
-    rc = APPNP_EINVAL;  // unsorted / duplicate / out-of-range column indices
-    goto done;
-  }
-  if (h_tot[0] > INT32_MAX) {
-    rc = APPNP_ERANGE;
-    goto done;
-  }
+  if (h_flags[0]) return APPNP_EINVAL;  // unsorted / duplicate / out-of-range column indices
+  if (h_tot[0] > INT32_MAX) return APPNP_ERANGE;
   g->symmetric = h_flags[1] == 0 ? 1 : 0;
   g->unit = h_flags[2] == 0 ? 1 : 0;
   g->nnz_hat = h_tot[0];
   g->nnz_local = h_tot[1];
   g->nnz_remote = h_tot[2];
-  APPNP_TRY(dalloc(&g->col, g->nnz_hat));
-  APPNP_TRY(dalloc(&g->val, g->nnz_hat));
+  APPNP_TRY(device_alloc(&g->col, g->nnz_hat));
+  APPNP_TRY(device_alloc(&g->val, g->nnz_hat));
+  CsrOut o_loc{}, o_rem{};
   if (split) {
-    APPNP_TRY(dalloc(&g->lcol, g->nnz_local));
-    APPNP_TRY(dalloc(&g->lval, g->nnz_local));
-    APPNP_TRY(dalloc(&g->rcol, g->nnz_remote));
-    APPNP_TRY(dalloc(&g->rval, g->nnz_remote));
-  }
-  o_all = CsrOut{g->row_ptr, g->col, g->val};
-  if (split) {
+    APPNP_TRY(device_alloc(&g->lcol, g->nnz_local));
+    APPNP_TRY(device_alloc(&g->lval, g->nnz_local));
+    APPNP_TRY(device_alloc(&g->rcol, g->nnz_remote));
+    APPNP_TRY(device_alloc(&g->rval, g->nnz_remote));
     o_loc = CsrOut{g->lrow_ptr, g->lcol, g->lval};
     o_rem = CsrOut{g->rrow_ptr, g->rcol, g->rval};
   }
   if (rows > 0) {
-    hipLaunchKernelGGL(k_fill, dim3(blocks_r), dim3(kBlock), 0, s, indptr, indices, vals, n, mode,
-                       g->dinv, row_lo, row_hi, o_all, o_loc, o_rem, flags);
+    hipLaunchKernelGGL(k_fill, dim3(blocks_for(rows)), dim3(kBlock), 0, s, indptr, indices, vals,
+                       n, mode, g->dinv, row_lo, row_hi, CsrOut{g->row_ptr, g->col, g->val}, o_loc,
+                       o_rem, flags);
     APPNP_TRY(hipGetLastError());
   }
   APPNP_TRY(hipStreamSynchronize(s));
-  (void)nnz;
-  rc = build_heavy(g->row_ptr, rows, kHeavyRow, s, &g->heavy, &g->n_heavy);
-  if (rc == APPNP_OK) rc = build_heavy(g->row_ptr, rows, kHubRow, s, &g->hub, &g->n_hub);
-
-done:
-  if (cnt) (void)hipFree(cnt);
-  if (cnt_l) (void)hipFree(cnt_l);
-  if (cnt_r) (void)hipFree(cnt_r);
-  if (bsum) (void)hipFree(bsum);
-  if (totals) (void)hipFree(totals);
-  if (flags) (void)hipFree(flags);
-  if (rc != APPNP_OK) graph_free(g);
-  return rc;
+  const int rc = build_heavy(g->row_ptr, rows, kHeavyRow, s, &g->heavy, &g->n_heavy);
+  if (rc != APPNP_OK) return rc;
+  return build_heavy(g->row_ptr, rows, kHubRow, s, &g->hub, &g->n_hub);
 }
 
 }  // namespace appnp

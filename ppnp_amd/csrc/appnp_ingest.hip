@@ -157,160 +157,131 @@ __global__ __launch_bounds__(kBlock) void k_fill_kept(const uint64_t* __restrict
     out_idx[o++] = new_id[(int32_t)(keys[p] & 0xffffffffu)];
 }
 
-struct Buffers {
-  uint64_t* keys = nullptr;
-  uint64_t* keys_sorted = nullptr;
-  void* tmp = nullptr;
-  unsigned* flags = nullptr;  // [0] err, [1] changed
-  unsigned int* uniq = nullptr;
-  int32_t *cnt = nullptr, *rp = nullptr, *parent = nullptr, *size = nullptr;
-  int32_t *keep = nullptr, *new_id = nullptr, *len = nullptr;
-  int64_t *bsum = nullptr, *tot = nullptr;
-  unsigned long long* best = nullptr;
-  ~Buffers() {
-    void* ps[] = {keys, keys_sorted, tmp, flags, uniq, cnt, rp, parent, size,
-                  keep, new_id, len, bsum, tot, best};
-    for (void* p : ps)
-      if (p) (void)hipFree(p);
-  }
-};
-
-template <typename T>
-hipError_t alloc(T** p, int64_t count) {
-  if (count <= 0) count = 1;
-  return hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T));
-}
-
-inline unsigned grid_of(int64_t n) {
-  return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock);
-}
-
 }  // namespace
 
 int standardize(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t n,
                 int64_t nnz, int select_lcc, hipStream_t s, appnp_csr* out) {
-#define TRY(x)                                                                              \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      return (e_ == hipErrorOutOfMemory || e_ == hipErrorMemoryAllocation) ? APPNP_ENOMEM   \
-                                                                           : APPNP_EDEVICE; \
-  } while (0)
-  Buffers b;
+  DeviceScratch tmp;
+  uint64_t *keys, *keys_sorted;
+  char* sort_tmp;
+  unsigned* flags;  // [0] err, [1] changed
+  unsigned int* uniq;
+  int32_t *rp, *parent, *size, *keep, *new_id, *len;
+  int64_t *bsum, *tot;
+  unsigned long long* best;
   const int64_t m = 2 * nnz;
   unsigned h_flags[2] = {0, 0};
   unsigned int h_uniq = 0;
   int64_t h_tot[2] = {0, 0};
   unsigned long long h_best = 0;
   out->n_in = n;
-  TRY(alloc(&b.flags, 2));
-  TRY(hipMemsetAsync(b.flags, 0, 2 * sizeof(unsigned), s));
-  TRY(alloc(&b.keys, m));
-  TRY(alloc(&b.keys_sorted, m));
-  TRY(alloc(&b.uniq, 1));
+  APPNP_TRY(tmp.get(&flags, 2));
+  APPNP_TRY(hipMemsetAsync(flags, 0, 2 * sizeof(unsigned), s));
+  APPNP_TRY(tmp.get(&keys, m));
+  APPNP_TRY(tmp.get(&keys_sorted, m));
+  APPNP_TRY(tmp.get(&uniq, 1));
   if (n > 0) {
-    hipLaunchKernelGGL(k_emit_keys, dim3(grid_of(n)), dim3(kBlock), 0, s, indptr, indices, vals,
-                       n, b.keys, b.flags);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_emit_keys, dim3(blocks_for(n)), dim3(kBlock), 0, s, indptr, indices, vals,
+                       n, keys, flags);
+    APPNP_TRY(hipGetLastError());
   }
   // sort + unique (sentinel keys sort last and collapse to one)
   unsigned end_bit = 64;
   {
     size_t tmp_sort = 0, tmp_uniq = 0;
-    TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, b.keys, b.keys_sorted, (size_t)m, 0u,
-                                 end_bit, s));
-    TRY(rocprim::unique(nullptr, tmp_uniq, b.keys_sorted, b.keys, b.uniq, (size_t)m,
-                        rocprim::equal_to<uint64_t>(), s));
-    TRY(alloc(reinterpret_cast<char**>(&b.tmp), (int64_t)std::max(tmp_sort, tmp_uniq)));
+    APPNP_TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, keys, keys_sorted, (size_t)m, 0u,
+                                       end_bit, s));
+    APPNP_TRY(rocprim::unique(nullptr, tmp_uniq, keys_sorted, keys, uniq, (size_t)m,
+                              rocprim::equal_to<uint64_t>(), s));
+    APPNP_TRY(tmp.get(&sort_tmp, (int64_t)std::max(tmp_sort, tmp_uniq)));
     if (m > 0) {
       size_t t1 = tmp_sort, t2 = tmp_uniq;
-      TRY(rocprim::radix_sort_keys(b.tmp, t1, b.keys, b.keys_sorted, (size_t)m, 0u, end_bit, s));
-      TRY(rocprim::unique(b.tmp, t2, b.keys_sorted, b.keys, b.uniq, (size_t)m,
-                          rocprim::equal_to<uint64_t>(), s));
+      APPNP_TRY(rocprim::radix_sort_keys(sort_tmp, t1, keys, keys_sorted, (size_t)m, 0u, end_bit,
+                                         s));
+      APPNP_TRY(rocprim::unique(sort_tmp, t2, keys_sorted, keys, uniq, (size_t)m,
+                                rocprim::equal_to<uint64_t>(), s));
     } else {
-      TRY(hipMemsetAsync(b.uniq, 0, sizeof(unsigned int), s));
+      APPNP_TRY(hipMemsetAsync(uniq, 0, sizeof(unsigned int), s));
     }
   }
-  TRY(hipMemcpyAsync(&h_uniq, b.uniq, sizeof(h_uniq), hipMemcpyDeviceToHost, s));
-  TRY(hipMemcpyAsync(h_flags, b.flags, sizeof(h_flags), hipMemcpyDeviceToHost, s));
-  TRY(hipStreamSynchronize(s));
+  APPNP_TRY(hipMemcpyAsync(&h_uniq, uniq, sizeof(h_uniq), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
   if (h_flags[0]) return APPNP_EINVAL;
   int64_t me = h_uniq;  // unique keys incl. at most one sentinel (sorted last)
   if (me > 0) {
     uint64_t last = 0;
-    TRY(hipMemcpy(&last, b.keys + (me - 1), sizeof(last), hipMemcpyDeviceToHost));
+    APPNP_TRY(hipMemcpy(&last, keys + (me - 1), sizeof(last), hipMemcpyDeviceToHost));
     if (last == kNoKey) --me;
   }
   // symmetric CSR of the whole graph
-  TRY(alloc(&b.rp, n + 1));
-  TRY(alloc(&b.bsum, scan_partials(n)));
-  TRY(alloc(&b.tot, 2));
-  hipLaunchKernelGGL(k_row_ptr, dim3(grid_of(n + 1)), dim3(kBlock), 0, s, b.keys, me, n, b.rp);
-  TRY(hipGetLastError());
+  APPNP_TRY(tmp.get(&rp, n + 1));
+  APPNP_TRY(tmp.get(&bsum, scan_partials(n)));
+  APPNP_TRY(tmp.get(&tot, 2));
+  hipLaunchKernelGGL(k_row_ptr, dim3(blocks_for(n + 1)), dim3(kBlock), 0, s, keys, me, n, rp);
+  APPNP_TRY(hipGetLastError());
   // components
-  TRY(alloc(&b.parent, n));
-  TRY(alloc(&b.size, n));
-  TRY(alloc(&b.best, 1));
-  TRY(hipMemsetAsync(b.size, 0, std::max<int64_t>(1, n) * sizeof(int32_t), s));
-  TRY(hipMemsetAsync(b.best, 0, sizeof(unsigned long long), s));
+  APPNP_TRY(tmp.get(&parent, n));
+  APPNP_TRY(tmp.get(&size, n));
+  APPNP_TRY(tmp.get(&best, 1));
+  APPNP_TRY(hipMemsetAsync(size, 0, std::max<int64_t>(1, n) * sizeof(int32_t), s));
+  APPNP_TRY(hipMemsetAsync(best, 0, sizeof(unsigned long long), s));
   if (n > 0) {
-    hipLaunchKernelGGL(k_init_parent, dim3(grid_of(n)), dim3(kBlock), 0, s, b.parent, n);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_init_parent, dim3(blocks_for(n)), dim3(kBlock), 0, s, parent, n);
+    APPNP_TRY(hipGetLastError());
   }
   if (select_lcc && me > 0) {
     for (int it = 0; it < 4096; ++it) {  // a few sweeps in practice; bounded regardless
       unsigned changed = 0;
-      TRY(hipMemsetAsync(b.flags + 1, 0, sizeof(unsigned), s));
-      hipLaunchKernelGGL(k_hook, dim3(grid_of(me)), dim3(kBlock), 0, s, b.keys, me, b.parent,
-                         b.flags + 1);
-      TRY(hipGetLastError());
-      TRY(hipMemcpyAsync(&changed, b.flags + 1, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-      TRY(hipStreamSynchronize(s));
+      APPNP_TRY(hipMemsetAsync(flags + 1, 0, sizeof(unsigned), s));
+      hipLaunchKernelGGL(k_hook, dim3(blocks_for(me)), dim3(kBlock), 0, s, keys, me, parent,
+                         flags + 1);
+      APPNP_TRY(hipGetLastError());
+      APPNP_TRY(hipMemcpyAsync(&changed, flags + 1, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+      APPNP_TRY(hipStreamSynchronize(s));
       if (!changed) break;
       if (it == 4095) return APPNP_EDEVICE;  // every sweep hooks >= 1 root: unreachable
     }
   }
   if (n > 0) {
-    hipLaunchKernelGGL(k_compress_count, dim3(grid_of(n)), dim3(kBlock), 0, s, b.parent, n,
-                       b.size);
-    hipLaunchKernelGGL(k_best, dim3(grid_of(n)), dim3(kBlock), 0, s, b.parent, b.size, n, b.best);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_compress_count, dim3(blocks_for(n)), dim3(kBlock), 0, s, parent, n, size);
+    hipLaunchKernelGGL(k_best, dim3(blocks_for(n)), dim3(kBlock), 0, s, parent, size, n, best);
+    APPNP_TRY(hipGetLastError());
   }
   // keep + renumber
-  TRY(alloc(&b.keep, n));
-  TRY(alloc(&b.new_id, n + 1));
+  APPNP_TRY(tmp.get(&keep, n));
+  APPNP_TRY(tmp.get(&new_id, n + 1));
   if (n > 0) {
-    hipLaunchKernelGGL(k_keep, dim3(grid_of(n)), dim3(kBlock), 0, s, b.parent, n, b.best,
-                       select_lcc ? 1 : 0, b.keep);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_keep, dim3(blocks_for(n)), dim3(kBlock), 0, s, parent, n, best,
+                       select_lcc ? 1 : 0, keep);
+    APPNP_TRY(hipGetLastError());
   }
-  TRY(exclusive_scan(b.keep, n, b.new_id, b.bsum, b.tot + 1, s));
-  TRY(hipMemcpyAsync(&h_tot[1], b.tot + 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TRY(hipMemcpyAsync(&h_best, b.best, sizeof(h_best), hipMemcpyDeviceToHost, s));
-  TRY(hipStreamSynchronize(s));
+  APPNP_TRY(exclusive_scan(keep, n, new_id, bsum, tot + 1, s));
+  APPNP_TRY(hipMemcpyAsync(&h_tot[1], tot + 1, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipMemcpyAsync(&h_best, best, sizeof(h_best), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
   const int64_t n_out = h_tot[1];
   out->n = n_out;
-  TRY(alloc(&out->node_map, n_out));
-  TRY(alloc(&b.len, n_out));
-  TRY(alloc(&out->indptr, n_out + 1));
+  APPNP_TRY(device_alloc(&out->node_map, n_out));
+  APPNP_TRY(tmp.get(&len, n_out));
+  APPNP_TRY(device_alloc(&out->indptr, n_out + 1));
   if (n > 0) {
-    hipLaunchKernelGGL(k_row_len_kept, dim3(grid_of(n)), dim3(kBlock), 0, s, b.rp, b.keep,
-                       b.new_id, n, b.len, out->node_map);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_row_len_kept, dim3(blocks_for(n)), dim3(kBlock), 0, s, rp, keep, new_id,
+                       n, len, out->node_map);
+    APPNP_TRY(hipGetLastError());
   }
-  TRY(exclusive_scan(b.len, n_out, out->indptr, b.bsum, b.tot, s));
-  TRY(hipMemcpyAsync(&h_tot[0], b.tot, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TRY(hipStreamSynchronize(s));
+  APPNP_TRY(exclusive_scan(len, n_out, out->indptr, bsum, tot, s));
+  APPNP_TRY(hipMemcpyAsync(&h_tot[0], tot, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
   out->nnz = h_tot[0];
-  TRY(alloc(&out->indices, out->nnz));
+  APPNP_TRY(device_alloc(&out->indices, out->nnz));
   if (n > 0) {
-    hipLaunchKernelGGL(k_fill_kept, dim3(grid_of(n)), dim3(kBlock), 0, s, b.keys, b.rp, b.keep,
-                       b.new_id, out->indptr, n, out->indices);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fill_kept, dim3(blocks_for(n)), dim3(kBlock), 0, s, keys, rp, keep,
+                       new_id, out->indptr, n, out->indices);
+    APPNP_TRY(hipGetLastError());
   }
-  TRY(hipStreamSynchronize(s));
+  APPNP_TRY(hipStreamSynchronize(s));
   return APPNP_OK;
-#undef TRY
 }
 
 namespace {
@@ -340,73 +311,67 @@ __global__ __launch_bounds__(kBlock) void k_low_word(const uint64_t* __restrict_
 // input rows in increasing order, so the result is canonical CSR.
 int csr_transpose(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t rows,
                   int64_t cols, int64_t nnz, hipStream_t s, appnp_csr* out) {
-#define TRY(x)                                                                              \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      return (e_ == hipErrorOutOfMemory || e_ == hipErrorMemoryAllocation) ? APPNP_ENOMEM   \
-                                                                           : APPNP_EDEVICE; \
-  } while (0)
-  Buffers b;
+  DeviceScratch tmp;
+  uint64_t *keys, *keys_sorted;
+  char* sort_tmp;
+  unsigned* flags;
   unsigned h_err = 0;
   out->n = cols;
   out->n_in = rows;
   out->nnz = nnz;
-  TRY(alloc(&b.flags, 2));
-  TRY(hipMemsetAsync(b.flags, 0, 2 * sizeof(unsigned), s));
-  TRY(alloc(&b.keys, nnz));
-  TRY(alloc(&b.keys_sorted, nnz));
+  APPNP_TRY(tmp.get(&flags, 2));
+  APPNP_TRY(hipMemsetAsync(flags, 0, 2 * sizeof(unsigned), s));
+  APPNP_TRY(tmp.get(&keys, nnz));
+  APPNP_TRY(tmp.get(&keys_sorted, nnz));
   if (rows > 0) {
-    hipLaunchKernelGGL(k_emit_t, dim3(grid_of(rows)), dim3(kBlock), 0, s, indptr, indices, rows,
-                       cols, b.keys, b.flags);
-    TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_emit_t, dim3(blocks_for(rows)), dim3(kBlock), 0, s, indptr, indices, rows,
+                       cols, keys, flags);
+    APPNP_TRY(hipGetLastError());
   }
-  TRY(alloc(&out->indptr, cols + 1));
-  TRY(alloc(&out->indices, nnz));
-  if (vals) TRY(alloc(&out->data, nnz));
+  APPNP_TRY(device_alloc(&out->indptr, cols + 1));
+  APPNP_TRY(device_alloc(&out->indices, nnz));
+  if (vals) APPNP_TRY(device_alloc(&out->data, nnz));
   if (nnz > 0) {
-    size_t tmp = 0;
+    size_t bytes = 0;
     if (vals) {
-      TRY(rocprim::radix_sort_pairs(nullptr, tmp, b.keys, b.keys_sorted, vals, out->data,
-                                    (size_t)nnz, 0u, 64u, s));
+      APPNP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_sorted, vals, out->data,
+                                          (size_t)nnz, 0u, 64u, s));
     } else {
-      TRY(rocprim::radix_sort_keys(nullptr, tmp, b.keys, b.keys_sorted, (size_t)nnz, 0u, 64u, s));
+      APPNP_TRY(rocprim::radix_sort_keys(nullptr, bytes, keys, keys_sorted, (size_t)nnz, 0u, 64u,
+                                         s));
     }
-    TRY(alloc(reinterpret_cast<char**>(&b.tmp), (int64_t)tmp));
+    APPNP_TRY(tmp.get(&sort_tmp, (int64_t)bytes));
     if (vals) {
-      TRY(rocprim::radix_sort_pairs(b.tmp, tmp, b.keys, b.keys_sorted, vals, out->data,
-                                    (size_t)nnz, 0u, 64u, s));
+      APPNP_TRY(rocprim::radix_sort_pairs(sort_tmp, bytes, keys, keys_sorted, vals, out->data,
+                                          (size_t)nnz, 0u, 64u, s));
     } else {
-      TRY(rocprim::radix_sort_keys(b.tmp, tmp, b.keys, b.keys_sorted, (size_t)nnz, 0u, 64u, s));
+      APPNP_TRY(rocprim::radix_sort_keys(sort_tmp, bytes, keys, keys_sorted, (size_t)nnz, 0u, 64u,
+                                         s));
     }
-    hipLaunchKernelGGL(k_low_word, dim3(grid_of(nnz)), dim3(kBlock), 0, s, b.keys_sorted, nnz,
+    hipLaunchKernelGGL(k_low_word, dim3(blocks_for(nnz)), dim3(kBlock), 0, s, keys_sorted, nnz,
                        out->indices);
-    TRY(hipGetLastError());
+    APPNP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_row_ptr, dim3(grid_of(cols + 1)), dim3(kBlock), 0, s, b.keys_sorted, nnz,
+  hipLaunchKernelGGL(k_row_ptr, dim3(blocks_for(cols + 1)), dim3(kBlock), 0, s, keys_sorted, nnz,
                      cols, out->indptr);
-  TRY(hipGetLastError());
-  TRY(hipMemcpyAsync(&h_err, b.flags, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  TRY(hipStreamSynchronize(s));
+  APPNP_TRY(hipGetLastError());
+  APPNP_TRY(hipMemcpyAsync(&h_err, flags, sizeof(h_err), hipMemcpyDeviceToHost, s));
+  APPNP_TRY(hipStreamSynchronize(s));
   return h_err ? APPNP_EINVAL : APPNP_OK;
-#undef TRY
 }
 
 // A_hat^T of a built graph, moved into the graph's t_* arrays.
 int graph_build_transpose(appnp_graph* g, hipStream_t s) {
-  appnp_csr t;
-  const int rc = csr_transpose(g->row_ptr, g->col, g->val, g->n, g->n, g->nnz_hat, s, &t);
-  if (rc != APPNP_OK) {
-    csr_free(&t);
-    return rc;
-  }
+  appnp_csr t;  // csr_transpose fills indptr, indices and data, never node_map
+  int rc = csr_transpose(g->row_ptr, g->col, g->val, g->n, g->n, g->nnz_hat, s, &t);
+  // whatever it allocated is the graph's from here, so graph_free releases it on failure too
   g->t_row_ptr = t.indptr;
   g->t_col = t.indices;
   g->t_val = t.data;
-  if (t.node_map) (void)hipFree(t.node_map);
-  int rc2 = build_heavy(g->t_row_ptr, g->n, kHeavyRow, s, &g->t_heavy, &g->t_n_heavy);
-  if (rc2 == APPNP_OK) rc2 = build_heavy(g->t_row_ptr, g->n, kHubRow, s, &g->t_hub, &g->t_n_hub);
-  return rc2;
+  if (rc != APPNP_OK) return rc;
+  rc = build_heavy(g->t_row_ptr, g->n, kHeavyRow, s, &g->t_heavy, &g->t_n_heavy);
+  if (rc != APPNP_OK) return rc;
+  return build_heavy(g->t_row_ptr, g->n, kHubRow, s, &g->t_hub, &g->t_n_hub);
 }
 
 void csr_free(appnp_csr* c) {

@@ -79,6 +79,7 @@ int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals
                 int64_t nnz, int mode, int64_t row_lo, int64_t row_hi, int split,
                 hipStream_t s, appnp_graph* g);
 void graph_free(appnp_graph* g);
+void graph_free_source_blocks(appnp_graph* g);
 int graph_build_shard_offsets(appnp_graph* g, int nshards, int64_t shard_rows, hipStream_t s);
 int graph_build_transpose(appnp_graph* g, hipStream_t s);
 int build_heavy(const int32_t* rp, int64_t rows, int32_t thr, hipStream_t s, int32_t** out,
@@ -133,6 +134,64 @@ void ktimer_begin(hipStream_t s);
 void ktimer_mark(hipStream_t s, int kind);
 
 inline size_t round_up(size_t x, size_t al) { return (x + al - 1) / al * al; }
+
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Workgroups of a thread-per-item launch of kBlock threads over n items (at least one).
+inline unsigned blocks_for(int64_t n) {
+  return n > kBlock ? (unsigned)((n + kBlock - 1) / kBlock) : 1u;
+}
+
+// hipError_t -> APPNP_E*, two ways.  build_err is the set-up builders' (graph, blocks, ingest):
+// they check their arguments before the first HIP call, so whatever is not an allocation failure
+// is the device's.  dev_err is the entry points' (appnp_capi.hip, appnp_dist.hip), which hand
+// caller-supplied sizes and pointers to the runtime: there hipErrorInvalidValue is the caller's
+// mistake, APPNP_EINVAL.
+inline int build_err(hipError_t e) {
+  if (e == hipSuccess) return APPNP_OK;
+  return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? APPNP_ENOMEM : APPNP_EDEVICE;
+}
+inline int dev_err(hipError_t e) { return e == hipErrorInvalidValue ? APPNP_EINVAL : build_err(e); }
+
+// Returns build_err(expr) from the enclosing builder when expr fails.  The builder's temporaries
+// live in a DeviceScratch and what it keeps lives in the appnp_graph / appnp_csr, which the
+// caller releases (graph_free / csr_free), so returning early leaks nothing.
+#define APPNP_TRY(expr)                                       \
+  do {                                                        \
+    const hipError_t e_ = (expr);                             \
+    if (e_ != hipSuccess) return ::appnp::build_err(e_);      \
+  } while (0)
+
+// count elements of device memory (one when count <= 0, so an empty input still gets a pointer)
+template <class T>
+inline hipError_t device_alloc(T** p, int64_t count) {
+  *p = nullptr;
+  return hipMalloc(reinterpret_cast<void**>(p), (size_t)(count > 0 ? count : 1) * sizeof(T));
+}
+
+// The temporary device buffers of one set-up call: freed when the scope ends, on every path.
+class DeviceScratch {
+ public:
+  DeviceScratch() = default;
+  DeviceScratch(const DeviceScratch&) = delete;
+  DeviceScratch& operator=(const DeviceScratch&) = delete;
+  ~DeviceScratch() {
+    for (int i = 0; i < n_; ++i) (void)hipFree(ptrs_[i]);
+  }
+  template <class T>
+  hipError_t get(T** p, int64_t count) {
+    *p = nullptr;
+    if (n_ == kMax) return hipErrorOutOfMemory;  // more buffers than any builder takes
+    const hipError_t e = device_alloc(p, count);
+    if (e == hipSuccess) ptrs_[n_++] = *p;
+    return e;
+  }
+
+ private:
+  static constexpr int kMax = 16;  // standardize takes 15
+  void* ptrs_[kMax];
+  int n_ = 0;
+};
 
 inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
 
