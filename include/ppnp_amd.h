@@ -53,7 +53,8 @@ extern "C" {
  * appnp_push_columns, with the timer kind APPNP_KT_PUSH; the top k straight from the push,
  * appnp_push_topk_workspace_bytes and appnp_push_topk; the per-minibatch slice of a sparse PPR
  * matrix with its transpose, appnp_csr_batch_workspace_bytes, appnp_csr_batch_count and
- * appnp_csr_batch_emit. */
+ * appnp_csr_batch_emit; whole rows of a device CSR with the transpose of the slice,
+ * appnp_csr_rows_workspace_bytes, appnp_csr_rows_count and appnp_csr_rows_emit. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -481,6 +482,63 @@ int appnp_csr_batch_emit(const int32_t* indptr, const int32_t* indices, const fl
                          int32_t* out_indices, float* out_vals, int64_t* sel, int32_t* t_indptr,
                          int32_t* t_indices, float* t_vals, void* ws, size_t ws_bytes,
                          void* stream);
+
+/*
+ * Whole rows of a device CSR (`M[idx]`: the rows X[sel] of a sparse attribute matrix, the rows
+ * ppr[idx_stop] of a sparse PPR matrix), optionally with the transpose of the slice: two calls
+ * with ONE read-back between them, the 16 bytes of `counts`, from which the caller sizes the
+ * outputs of the second.
+ *   M: a CSR [rows, cols], int32 indptr / indices, fp32 vals.  indices / vals may be NULL for a
+ *      matrix without entries: every row is then taken as empty.
+ *   idx: b row indices (int64, device memory), in any order, duplicates allowed.  Taken row p is
+ *      M[idx[p]], copied whole: its entries keep their order, columns are NOT relabelled, values
+ *      are copied bit for bit.  An index outside [0, rows) contributes an empty row and is counted
+ *      in counts[1]; the kernels never read outside indptr.
+ *   appnp_csr_rows_count writes
+ *      out_indptr: int32 [b + 1], the row pointer of the [b, cols] result;
+ *      counts: int64 [2] = entries of the result (nnz_out), indices outside [0, rows);
+ *   from indptr alone (O(b) work), in ONE single-workgroup launch that folds the row lengths,
+ *   their scan (APPNP_CSR_BATCH_SCAN_PASS items per pass) and the out-of-range count: it needs no
+ *   workspace and nothing is cleared before it.
+ *   appnp_csr_rows_emit, after it on the same stream, with nnz_out = counts[0] and the out_indptr
+ *   count wrote, writes
+ *      out_indices int32 [nnz_out], out_vals fp32 [nnz_out]: the CSR [b, cols];
+ *   and, when t_indptr != NULL,
+ *      t_indptr int32 [cols + 1], t_indices int32 [nnz_out], t_vals fp32 [nnz_out]: the canonical
+ *      CSR [cols, b] of its transpose, the entries of a row ascending by batch position p (equal
+ *      p: in their order within row p) -- exactly what appnp_csr_transpose returns for the slice,
+ *      bit for bit.
+ *   With t_indptr == NULL only the copy runs (one launch; t_indices, t_vals and ws are not used):
+ *   the route for a slice that is never differentiated.
+ *   An entry whose column lies outside [0, cols) is copied as it is and left out of the transpose;
+ *   the values of such a malformed matrix, and those for sizes other than count reported, are
+ *   unspecified, but there is never an access outside the buffers as sized by the arguments.
+ *   Outputs of size 0 may be NULL.
+ *   ws: only for the transpose of a slice with entries (t_indptr != NULL, nnz_out > 0, cols > 0):
+ *      4-byte aligned, appnp_csr_rows_workspace_bytes(cols, nnz_out) bytes: cols cursors and
+ *      2 nnz_cap words for the (entry, row) pairs, rounded up to 256 bytes.  The size is monotone
+ *      in each argument and 0 for an empty shape (cols <= 0 or nnz_cap <= 0).
+ * Launches on `stream`: count is one; emit is one without the transpose, and with it five: a clear
+ * of t_indptr (a kernel, not a memset node), the wave-per-row copy that also counts each column
+ * with integer atomics, and the t_indptr scan, scatter and segment sort of appnp_csr_batch_emit
+ * (the same kernels, over all cols columns).  No workgroup waits for another; integer atomics
+ * only, so two runs give the same bits.  Both calls are stream-ordered and make no allocation and
+ * no host synchronisation.  The per-launch timer records their launches as APPNP_KT_COPY.
+ * APPNP_EINVAL, before any device call: rows, cols or b negative, cols or b > INT32_MAX; for emit
+ * also nnz_out negative or > INT32_MAX.  Then APPNP_OK, with nothing written, when b == 0.  Then
+ * APPNP_EINVAL for a NULL indptr / idx / out_indptr, a NULL counts (count), a NULL array of
+ * nnz_out > 0 elements (emit; t_indices / t_vals only with t_indptr), and, where the workspace is
+ * used, one that is NULL, too small or misaligned.
+ */
+size_t appnp_csr_rows_workspace_bytes(int64_t cols, int64_t nnz_cap);
+int appnp_csr_rows_count(const int32_t* indptr, const int32_t* indices, const float* vals,
+                         int64_t rows, int64_t cols, const int64_t* idx, int64_t b,
+                         int32_t* out_indptr, int64_t* counts, void* stream);
+int appnp_csr_rows_emit(const int32_t* indptr, const int32_t* indices, const float* vals,
+                        int64_t rows, int64_t cols, const int64_t* idx, int64_t b,
+                        const int32_t* out_indptr, int64_t nnz_out, int32_t* out_indices,
+                        float* out_vals, int32_t* t_indptr, int32_t* t_indices, float* t_vals,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /*
  * One iteration on the held rows:  Zout[i-row_lo] = (1-alpha) sum_j (M_k o A_hat)_ij Zin[j]

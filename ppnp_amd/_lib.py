@@ -123,6 +123,16 @@ _SIGS = {
         [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
          _vp, _sz, _vp],
     ),
+    "appnp_csr_rows_workspace_bytes": (_sz, [_i64, _i64]),
+    "appnp_csr_rows_count": (
+        _i32,
+        [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    ),
+    "appnp_csr_rows_emit": (
+        _i32,
+        [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+         _vp],
+    ),
     "appnp_plan_launch": (_i32, [_vp, _vp]),
     "appnp_plan_destroy": (None, [_vp]),
     "appnp_dist_create": (

@@ -34,6 +34,12 @@
 // row (and counted), a column outside [0, cols) is never selected, and every store is guarded by
 // the size of its output, so a caller that passes sizes other than those `counts` reported gets
 // unspecified values, never an access outside its buffers.
+//
+// appnp_csr_rows_count / appnp_csr_rows_emit take whole rows of a CSR, M[idx],
+// with no column selected or relabelled: count is ONE single-workgroup launch (lengths from indptr,
+// their scan, the out-of-range count: no workspace, nothing to clear), emit a wave-per-row copy
+// and, for the transpose, a clear of t_indptr before it and tscan, scatter and sort after it, over
+// all cols columns.
 #include <algorithm>
 
 #include "appnp_internal.h"
@@ -358,6 +364,70 @@ __global__ __launch_bounds__(kBlock) void k_batch_sort(BatchArgs a) {
   }
 }
 
+// ---- whole rows of a CSR (appnp_csr_rows_count / _emit) ----------------------
+// The same BatchArgs with n_sel = cols (no column is relabelled), so that tscan, scatter and sort
+// above serve its transpose unchanged.
+
+// Entries of taken row p as indptr gives them; an index outside [0, rows) adds to `oob`.
+__device__ __forceinline__ uint32_t taken_len(const BatchArgs& a, int64_t p,
+                                              unsigned long long& oob) {
+  int32_t s = 0, e = 0;
+  bool in_range;
+  const bool any = taken_row(a, p, s, e, in_range);
+  oob += in_range ? 0ull : 1ull;
+  return any ? (uint32_t)((int64_t)e - s) : 0u;
+}
+
+// One workgroup: the row lengths from indptr, their exclusive scan (out_indptr) and the indices
+// outside [0, rows), with no state in memory before it: nothing to clear.
+__global__ __launch_bounds__(kScanThreads) void k_rows_count(BatchArgs a) {
+  __shared__ unsigned long long wsum[kScanWaves];
+  __shared__ unsigned long long oob_all;
+  if (threadIdx.x == 0) oob_all = 0ull;
+  unsigned long long oob = 0;  // of the rows this thread loads
+  const unsigned long long nnz = scan_loop(
+      a.b, wsum, [&](int64_t i) { return taken_len(a, i, oob); },
+      [&](int64_t i, unsigned long long ex, uint32_t) {
+        a.out_indptr[i] = (int32_t)std::min<unsigned long long>(ex, INT32_MAX);
+      });
+  if (oob != 0ull) atomicAdd(&oob_all, oob);  // after scan_loop's barriers: oob_all is zero
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.out_indptr[a.b] = (int32_t)std::min<unsigned long long>(nnz, INT32_MAX);
+    a.counts[0] = (int64_t)nnz;  // the caller refuses nnz >= 2^31
+    a.counts[1] = (int64_t)oob_all;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_rows_clear(BatchArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i <= a.cols; i += stride)
+    a.t_indptr[i] = 0;  // the column counts
+}
+
+// A wave per taken row: the row as it is.  kT: also counts each entry's column into t_indptr; an
+// entry whose column lies outside [0, cols) is copied and not counted (scatter skips it too).
+template <bool kT>
+__global__ __launch_bounds__(kBlock) void k_rows_copy(BatchArgs a) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t p = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  if (p >= a.b) return;  // whole wave
+  int32_t s = 0, e = 0;
+  bool in_range;
+  if (!taken_row(a, p, s, e, in_range)) return;
+  const int64_t base = a.out_indptr[p];
+  for (int64_t q = (int64_t)s + lane; q < e; q += kWave) {
+    const int64_t pos = base + (q - s);
+    if (pos < 0 || pos >= a.nnz_out) continue;
+    const int32_t j = a.indices[q];
+    a.out_indices[pos] = j;
+    a.out_vals[pos] = a.vals[q];
+    if (kT && j >= 0 && j < a.cols) atomicAdd(reinterpret_cast<uint32_t*>(&a.t_indptr[j + 1]), 1u);
+  }
+}
+
+inline size_t rows_ws_words(int64_t cols, int64_t nnz) { return (size_t)cols + 2 * (size_t)nnz; }
+
 inline int64_t bitmap_words(int64_t cols) { return (cols + 31) / 32; }
 
 // words of the workspace parts, in their order
@@ -501,6 +571,108 @@ extern "C" int appnp_csr_batch_emit(const int32_t* indptr, const int32_t* indice
                       [&] { hipLaunchKernelGGL(k_batch_scatter, grid, block, 0, s, a); });
   if (rc == APPNP_OK) {
     const dim3 seg_grid((unsigned)((n_sel + kSegsPerBlock - 1) / kSegsPerBlock));
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_batch_sort, seg_grid, block, 0, s, a); });
+  }
+  return rc;
+}
+
+extern "C" size_t appnp_csr_rows_workspace_bytes(int64_t cols, int64_t nnz_cap) {
+  using namespace appnp;
+  if (cols <= 0 || nnz_cap <= 0 || cols > INT32_MAX || nnz_cap > INT32_MAX) return 0;
+  return round_up(rows_ws_words(cols, nnz_cap) * sizeof(uint32_t), 256);
+}
+
+extern "C" int appnp_csr_rows_count(const int32_t* indptr, const int32_t* indices,
+                                    const float* vals, int64_t rows, int64_t cols,
+                                    const int64_t* idx, int64_t b, int32_t* out_indptr,
+                                    int64_t* counts, void* stream) {
+  using namespace appnp;
+  if (bad_shape(rows, cols, b)) return APPNP_EINVAL;
+  if (b == 0) return APPNP_OK;
+  if (!indptr || !idx || !out_indptr || !counts) return APPNP_EINVAL;
+
+  BatchArgs a{};
+  a.indptr = indptr;
+  a.indices = indices;
+  a.vals = vals;
+  a.rows = rows;
+  a.cols = cols;
+  a.idx = idx;
+  a.b = b;
+  a.out_indptr = out_indptr;
+  a.counts = counts;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return timed_launch(s, APPNP_KT_COPY, [&] {
+    hipLaunchKernelGGL(k_rows_count, dim3(1), dim3(kScanThreads), 0, s, a);
+  });
+}
+
+extern "C" int appnp_csr_rows_emit(const int32_t* indptr, const int32_t* indices,
+                                   const float* vals, int64_t rows, int64_t cols,
+                                   const int64_t* idx, int64_t b, const int32_t* out_indptr,
+                                   int64_t nnz_out, int32_t* out_indices, float* out_vals,
+                                   int32_t* t_indptr, int32_t* t_indices, float* t_vals, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  using namespace appnp;
+  if (bad_shape(rows, cols, b) || nnz_out < 0 || nnz_out > INT32_MAX) return APPNP_EINVAL;
+  if (b == 0) return APPNP_OK;
+  if (!indptr || !idx || !out_indptr) return APPNP_EINVAL;
+  if (nnz_out > 0 && (!indices || !vals || !out_indices || !out_vals)) return APPNP_EINVAL;
+  const bool chain = t_indptr && nnz_out > 0 && cols > 0;  // the transpose holds entries
+  if (chain) {
+    if (!t_indices || !t_vals || !ws) return APPNP_EINVAL;
+    if (ws_bytes < appnp_csr_rows_workspace_bytes(cols, nnz_out)) return APPNP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) % sizeof(uint32_t) != 0) return APPNP_EINVAL;
+  }
+
+  BatchArgs a{};
+  a.indptr = indptr;
+  a.indices = indices;
+  a.vals = vals;
+  a.rows = rows;
+  a.cols = cols;
+  a.idx = idx;
+  a.b = b;
+  a.nnz_out = nnz_out;
+  a.n_sel = cols;  // every column keeps its id: tscan, scatter and sort run over all of them
+  a.out_indptr = const_cast<int32_t*>(out_indptr);  // read only
+  a.out_indices = out_indices;
+  a.out_vals = out_vals;
+  a.t_indptr = t_indptr;
+  a.t_indices = t_indices;
+  a.t_vals = t_vals;
+  if (chain) {
+    a.cursor = static_cast<uint32_t*>(ws);
+    a.tkey = reinterpret_cast<int32_t*>(a.cursor + cols);
+    a.trow = a.tkey + nnz_out;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 block(kBlock), grid(grid_rows(b));
+
+  int rc = APPNP_OK;
+  if (t_indptr) {
+    const int64_t blocks = std::min<int64_t>((cols + kBlock) / kBlock, 65536);
+    rc = timed_launch(s, APPNP_KT_COPY, [&] {
+      hipLaunchKernelGGL(k_rows_clear, dim3((unsigned)blocks), block, 0, s, a);
+    });
+  }
+  if (nnz_out == 0 || rc != APPNP_OK) return rc;
+  rc = timed_launch(s, APPNP_KT_COPY, [&] {
+    if (chain)
+      hipLaunchKernelGGL(k_rows_copy<true>, grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL(k_rows_copy<false>, grid, block, 0, s, a);
+  });
+  if (!chain || rc != APPNP_OK) return rc;
+  rc = timed_launch(s, APPNP_KT_COPY, [&] {
+    hipLaunchKernelGGL(k_batch_tscan, dim3(1), dim3(kScanThreads), 0, s, a);
+  });
+  if (rc == APPNP_OK)
+    rc = timed_launch(s, APPNP_KT_COPY,
+                      [&] { hipLaunchKernelGGL(k_batch_scatter, grid, block, 0, s, a); });
+  if (rc == APPNP_OK) {
+    const dim3 seg_grid((unsigned)((cols + kSegsPerBlock - 1) / kSegsPerBlock));
     rc = timed_launch(s, APPNP_KT_COPY,
                       [&] { hipLaunchKernelGGL(k_batch_sort, seg_grid, block, 0, s, a); });
   }

@@ -456,6 +456,55 @@ def csr_batch(P, idx):
     return out_indptr, out_indices, out_vals, sel, (t_indptr, t_indices, t_vals)
 
 
+def csr_rows(M, idx, transpose: bool = True):
+    """``M[idx]`` on a device CSR ``M`` (a ``SparseFeatures``) via ``appnp_csr_rows_count`` /
+    ``_emit``: the rows ``idx`` (int64, any order, duplicates allowed) copied whole, columns not
+    relabelled, values bit for bit.  Returns ``(indptr int32 [b + 1], indices int32, data fp32,
+    t)``; ``t`` is ``(t_indptr, t_indices, t_data)``, the canonical CSR [cols x b] of the
+    transpose, bit for bit ``appnp_csr_transpose`` of the slice, or ``None`` with
+    ``transpose=False`` (then emit is one launch: the route under ``no_grad``).  One read-back per
+    call (the two counts, 16 bytes) sizes the outputs; everything else is stream-ordered on the
+    current stream.  ``IndexError`` for an index outside [0, rows), ``ValueError`` for 2^31
+    entries or more.  See include/ppnp_amd.h."""
+    dev = M.device
+    if dev.type != "cuda":
+        raise ValueError("csr_rows needs a matrix on a GPU (there is no CPU fallback)")
+    idx = torch.as_tensor(idx, device=dev).long().contiguous().reshape(-1)
+    rows, cols = M.shape
+    b = int(idx.numel())
+    i32 = {"dtype": torch.int32, "device": dev}
+    if b == 0:  # the library writes nothing
+        empty = torch.empty(0, **i32)
+        t = (torch.zeros(cols + 1, **i32), empty.clone(), empty.float()) if transpose else None
+        return torch.zeros(1, **i32), empty, empty.float(), t
+    out_indptr = torch.empty(b + 1, **i32)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    src = (_vp(M.indptr), _vp(M.indices), _vp(M.data), rows, cols, _vp(idx), b)
+    with torch.cuda.device(dev):
+        rc = lib.appnp_csr_rows_count(*src, _vp(out_indptr), _vp(counts), _stream(dev))
+    _lib.check("appnp_csr_rows_count", rc)
+    nnz, bad = counts.cpu().tolist()  # the one read-back: the sizes depend on the data
+    if bad:
+        raise IndexError(f"csr_rows: {bad} of {b} indices lie outside [0, {rows})")
+    if nnz >= 2**31:
+        raise ValueError(f"csr_rows: {nnz} entries exceed the int32 CSR index range")
+    out_indices = torch.empty(nnz, **i32)
+    out_vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+    t, ws, need = None, None, 0
+    if transpose:
+        t = (torch.empty(cols + 1, **i32), torch.empty(nnz, **i32),
+             torch.empty(nnz, dtype=torch.float32, device=dev))
+        need = int(lib.appnp_csr_rows_workspace_bytes(cols, nnz))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    tp = [_vp(x) for x in t] if transpose else [None, None, None]
+    with torch.cuda.device(dev):
+        rc = lib.appnp_csr_rows_emit(*src, _vp(out_indptr), nnz, _vp(out_indices), _vp(out_vals),
+                                     *tp, _vp(ws), need, _stream(dev))
+    _lib.check("appnp_csr_rows_emit", rc)
+    return out_indptr, out_indices, out_vals, t
+
+
 def step(graph: Graph, Zin: torch.Tensor, H: torch.Tensor, out: torch.Tensor, k: int,
          alpha: float, part: int = _lib.PART_ALL, partial: torch.Tensor | None = None,
          p_drop: float = 0.0, seed: int = 0) -> torch.Tensor:

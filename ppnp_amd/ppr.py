@@ -164,8 +164,18 @@ class SparsePPR(SparseFeatures):
         ip[1:] = lens.cumsum(0)
         return ip
 
-    def rows(self, idx) -> "SparsePPR":
-        """The rows ``idx`` (in that order) over all N columns: ``ppr[idx]``."""
+    def rows(self, idx, slicer: str = "torch") -> "SparsePPR":
+        """The rows ``idx`` (in that order) over all N columns: ``ppr[idx]``.
+
+        ``slicer="device"``: the same matrix, bit for bit, from ``ops.csr_rows`` (HIP kernels, one
+        16-byte read-back), with its ``_t`` set.  GPU matrices only."""
+        if slicer not in ("torch", "device"):
+            raise ValueError(f"slicer must be 'torch' or 'device', got {slicer!r}")
+        if slicer == "device":
+            if self.device.type != "cuda":
+                raise ValueError("slicer='device' needs a matrix on a GPU (there is no CPU "
+                                 "fallback); use slicer='torch'")
+            return self._rows_device(idx)
         lens, pos = self._take(idx)
         return SparsePPR(self._indptr(lens), self.indices[pos], self.data[pos],
                          (lens.numel(), self.shape[1]), device=self.device)

@@ -80,6 +80,26 @@ class SparseFeatures:
             self._t = (ip, ix, dv)
         return self._t
 
+    def _rows_device(self, idx, transpose=True):
+        """``self[idx]`` from ``ops.csr_rows`` as the same class, its transpose already set."""
+        from .ops import csr_rows
+
+        if self.device.type != "cuda":
+            raise ValueError("taking rows on the device needs a matrix on a GPU (there is no "
+                             "CPU fallback)")
+        indptr, indices, data, t = csr_rows(self, idx, transpose)
+        sub = type(self)(indptr, indices, data, (indptr.numel() - 1, self.shape[1]),
+                         device=self.device)
+        sub._t = t
+        return sub
+
+    def rows(self, idx):
+        """The rows ``idx`` (int64, any order, duplicates allowed) as a SparseFeatures
+        [len(idx), F]: ``X[sel]`` of a minibatch, from the HIP kernels of ``ops.csr_rows`` (one
+        16-byte read-back).  Its transpose arrives with it, so the backward of ``sparse_linear``
+        does not build one.  GPU matrices only."""
+        return self._rows_device(idx)
+
     def to_dense(self):
         return torch.sparse_csr_tensor(self.indptr.long(), self.indices.long(), self.data,
                                        size=self.shape).to_dense()

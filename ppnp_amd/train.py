@@ -24,7 +24,10 @@ those rows by forward push, whose work per source does not grow with N; ``--ppr-
 also selects them straight from the push's lists, with no dense block of columns.
 ``--batch-slice device`` cuts each minibatch out of that matrix with the HIP kernels of
 ``ops.csr_batch`` (one 24-byte read-back per batch, the transpose for the backward included)
-instead of torch operations; the numbers are the same bits.
+instead of torch operations; the numbers are the same bits.  With it ``--sparse-x`` keeps the
+attribute matrix a CSR on the GPU in minibatch training too: ``X[sel]`` becomes ``X.rows(sel)``
+and the stopping and validation rows of the PPR matrix ``P.rows(idx, slicer="device")``
+(``ops.csr_rows``, one 16-byte read-back each, the transpose included).
 """
 
 from __future__ import annotations
@@ -243,14 +246,16 @@ def _run_batches(model, opt, early_stopping, X, idx, y, args, stats=None):
     torch.cuda.synchronize()
     if stats is not None:
         stats["ppr_build"] = time.time() - t0
-    P_stop, P_valid = P.rows(idx_stop), P.rows(idx_valid)
+    sparse_x = not torch.is_tensor(X)  # a SparseFeatures: parse_args allows it with 'device' only
+    rows_slicer = "device" if sparse_x else "torch"
+    P_stop, P_valid = P.rows(idx_stop, slicer=rows_slicer), P.rows(idx_valid, slicer=rows_slicer)
     t = time.time()
     for epoch in range(args.max_epochs):
         model.train()
         for idx_batch, y_batch in loader:
             ppr_sub, sel = P.batch(idx_batch.to(X.device),
                                    slicer=getattr(args, "batch_slice", "torch"))
-            logits = model(X[sel], idx=None, ppr=ppr_sub)
+            logits = model(X.rows(sel) if sparse_x else X[sel], idx=None, ppr=ppr_sub)
             loss = F.cross_entropy(logits, y_batch.to(X.device))
             loss = loss + args.reg_lambda / 2 * model.get_norm()
             opt.zero_grad()
@@ -334,9 +339,10 @@ def parse_args(argv=None):
             p.error("--batch-size needs a positive value and a positive --ppr-topk")
         if args.model != "appnp":
             p.error("--batch-size needs --model appnp")
-        if args.sparse_x:
+        if args.sparse_x and args.batch_slice != "device":
             p.error("--batch-size cannot be combined with --sparse-x: a minibatch takes the "
-                    "rows X[sel], which needs a dense X")
+                    "rows X[sel], which needs a dense X (or --batch-slice device, which takes "
+                    "them from the sparse X with the HIP kernels of ops.csr_rows)")
         if args.ppr_eps is not None and not 0.0 < args.ppr_eps < 1.0:
             p.error("--ppr-eps must lie in (0, 1)")
     elif args.ppr_topk is not None:
