@@ -54,7 +54,9 @@ extern "C" {
  * appnp_push_topk_workspace_bytes and appnp_push_topk; the per-minibatch slice of a sparse PPR
  * matrix with its transpose, appnp_csr_batch_workspace_bytes, appnp_csr_batch_count and
  * appnp_csr_batch_emit; whole rows of a device CSR with the transpose of the slice,
- * appnp_csr_rows_workspace_bytes, appnp_csr_rows_count and appnp_csr_rows_emit. */
+ * appnp_csr_rows_workspace_bytes, appnp_csr_rows_count and appnp_csr_rows_emit; polynomial
+ * propagation with coefficients in device memory, appnp_poly_workspace_bytes, appnp_poly and
+ * appnp_poly_bwd. */
 #define PPNP_AMD_ABI_VERSION 2
 
 typedef struct appnp_graph appnp_graph;
@@ -296,6 +298,50 @@ int appnp_solve(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int6
 int appnp_solve_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, void* dH, int64_t ld_dh,
                     int64_t f, int dtype, int iters, float alpha, void* ws, size_t ws_bytes,
                     void* stream);
+
+/*
+ * Polynomial propagation (GPR-GNN; the generalisation of the APPNP series):
+ *
+ *   Z = sum_{k=0..K} gamma_k A_hat^k H
+ *
+ * gamma_k = alpha (1-alpha)^k (k < K), gamma_K = (1-alpha)^K is appnp_propagate(K, alpha);
+ * gamma_k = e^-t t^k / k! is heat-kernel diffusion; a trained gamma is GPR-GNN, negative
+ * (high-pass) coefficients included.  coef: K + 1 fp32 values in DEVICE memory, read by the
+ * kernels only, so a trainable gamma never crosses to the host and a captured call follows a
+ * refill of it.
+ *
+ * appnp_poly      T_0 = H, T_k = A_hat T_{k-1}, Z = sum gamma_k T_k: K launches of the fused SpMM
+ *                 kernel (APPNP_KT_STEP; the first also forms gamma_0 H, the last stores no T_K);
+ *                 K = 0: one row-scale launch (APPNP_KT_COPY), Z = gamma_0 H.
+ * appnp_poly_bwd  From <dZ, A_hat^k H> = <(A_hat^T)^k dZ, H>: G_0 = dZ, G_k = A_hat^T G_{k-1},
+ *                 dH = sum gamma_k G_k and dcoef[k] = <G_k, H>; no power of A_hat times H is stored
+ *                 or recomputed.  One row launch (dH = gamma_0 dZ and the row dots of <dZ, H>), K
+ *                 step launches whose epilogue also leaves one fp32 partial of <G_k, H> per (column
+ *                 slab, row), and K + 1 reduce launches (APPNP_KT_COPY) of one fixed shape: 1024
+ *                 threads, thread t sums partials t, t + 1024, ... in fp64, then a halving tree.
+ *                 No floating-point atomics: dH and dcoef are bitwise reproducible.  dcoef: K + 1
+ *                 fp32 in device memory, or NULL: then no dot is computed and H may be NULL.
+ *                 A_hat^T is A_hat itself for 'sym' on a symmetric graph, else the transpose built
+ *                 with APPNP_GRAPH_TRANSPOSE; APPNP_ENOTSUP if neither is available.
+ * appnp_poly_workspace_bytes  bytes of `ws` for either call (with_dcoef: appnp_poly_bwd with a
+ *                 non-NULL dcoef): up to two [n, f] buffers and the partial dots.  Monotone in f
+ *                 and K; 0 for an empty shape or invalid arguments.
+ * Both calls are stream-ordered, allocate nothing and never synchronise.
+ * Limits: a full graph ('sym' or 'rw', directed graphs included, for the forward); H != Z,
+ * dZ != dH, H != dH; 0 <= K <= APPNP_POLY_MAX_K; fp32 only (APPNP_ENOTSUP for bf16); no edge
+ * dropout (a mask per step breaks the identity behind dcoef).  Rows are always gathered whole:
+ * the source-blocked remainder pass is not used, also on a graph that has the copy, and
+ * appnp_graph_source_block_layout's launch count does not move.  Arguments are validated before
+ * any device call, in the order of appnp_solve; an empty shape (n = 0 or f = 0) is APPNP_OK.
+ */
+#define APPNP_POLY_MAX_K 1024
+size_t appnp_poly_workspace_bytes(const appnp_graph* g, int64_t f, int K, int with_dcoef);
+int appnp_poly(const appnp_graph* g, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
+               int64_t f, int dtype, int K, const float* coef, void* ws, size_t ws_bytes,
+               void* stream);
+int appnp_poly_bwd(const appnp_graph* g, const void* dZ, int64_t ld_dz, const void* H,
+                   int64_t ld_h, void* dH, int64_t ld_dh, float* dcoef, int64_t f, int dtype,
+                   int K, const float* coef, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Sparse top-k PPR rows (batch-main.py:113-117, 134-152: the dense `ppr.topk` and the per-batch

@@ -7,8 +7,9 @@ model.py:63, as hand-written HIP kernels behind the C ABI in include/ppnp_amd.h.
 
 from . import _lib
 from .graph import Graph
-from .model import APPNP, PPNP, CustomLinear
-from .ops import (SolvePlan, propagate, propagate_backward, propagate_forward, solve,
+from .model import APPNP, GPRGNN, PPNP, CustomLinear
+from .ops import (SolvePlan, heat_coefficients, poly, poly_backward, poly_forward,
+                  ppr_coefficients, propagate, propagate_backward, propagate_forward, solve,
                   solve_backward, solve_forward, solve_iterations, split_copy, step, step_split,
                   topk_columns)
 from .ppr import SparsePPR, sparsified_ppr, topk_rows
@@ -16,12 +17,18 @@ from .sparse import SparseFeatures, sparse_linear
 
 __all__ = [
     "APPNP",
+    "GPRGNN",
     "PPNP",
     "CustomLinear",
     "Graph",
     "propagate",
     "propagate_forward",
     "propagate_backward",
+    "poly",
+    "poly_forward",
+    "poly_backward",
+    "ppr_coefficients",
+    "heat_coefficients",
     "solve",
     "solve_forward",
     "solve_backward",

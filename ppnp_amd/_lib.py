@@ -93,6 +93,12 @@ _SIGS = {
     "appnp_solve_weights": (_i32, [_f32, _i32, C.POINTER(C.c_double)]),
     "appnp_solve": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, _vp]),
     "appnp_solve_bwd": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, _vp]),
+    "appnp_poly_workspace_bytes": (_sz, [_vp, _i64, _i32, _i32]),
+    "appnp_poly": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "appnp_poly_bwd": (
+        _i32,
+        [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp],
+    ),
     "appnp_plan_create_solve": (
         _i32,
         [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _sz, C.POINTER(_vp)],

@@ -103,15 +103,7 @@ using appnp::ktimer_mark;
 using appnp::as_stream;
 using appnp::dev_err;
 
-// One launch (or copy) on `s` between the kernel timer's two events, tagged `kind` (APPNP_KT_*).
-// Every launch of this unit's propagation entry points goes through here.
-template <typename Launch>
-inline int timed(hipStream_t s, int kind, Launch launch) {
-  ktimer_begin(s);
-  const int rc = dev_err(launch());
-  ktimer_mark(s, kind);
-  return rc;
-}
+using appnp::timed;  // appnp_internal.h
 
 inline int timed_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s,
                       int kind = APPNP_KT_STEP) {
@@ -148,39 +140,8 @@ int check_common(const appnp_graph* g, int64_t f, int dtype, int K, float alpha,
   return APPNP_OK;
 }
 
-StepArgs base_args(const appnp_graph* g, int64_t f, float alpha) {
-  StepArgs a{};
-  a.row_ptr = g->row_ptr;
-  a.col = g->col;
-  a.val = g->val;
-  a.n_rows = g->row_hi - g->row_lo;
-  a.nnz = g->nnz_hat;
-  a.nnz_rows = g->nnz_hat;  // a step over part of the rows' entries overrides nnz only
-  a.zin_rows = g->n;
-  a.row_lo = g->row_lo;
-  a.f = (int32_t)f;
-  a.scale = 1.0f - alpha;
-  a.alpha = alpha;
-  a.drop_scale = 1.0f;
-  a.heavy = g->heavy;
-  a.n_heavy = g->n_heavy;
-  a.heavy_thr = appnp::kHeavyRow;
-  a.hub = g->hub;
-  a.n_hub = g->n_hub;
-  return a;
-}
-
-// A_hat^T for the adjoints of a graph whose A_hat is not symmetric: the transposed CSR built at
-// creation (APPNP_GRAPH_TRANSPOSE) and its heavy / hub rows
-void use_transpose(StepArgs& a, const appnp_graph* g) {
-  a.row_ptr = g->t_row_ptr;
-  a.col = g->t_col;
-  a.val = g->t_val;
-  a.heavy = g->t_heavy;
-  a.n_heavy = g->t_n_heavy;
-  a.hub = g->t_hub;
-  a.n_hub = g->t_n_hub;
-}
+using appnp::base_args;  // appnp_internal.h
+using appnp::use_transpose;
 
 // The heavy / hub lists describe the whole held rows: a step over part of their entries (the
 // LOCAL / REMOTE half, a shard range) runs without them.

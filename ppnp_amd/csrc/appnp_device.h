@@ -24,8 +24,17 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 //                                                    aux = Z_{k-1} in the storage type, may be
 //                                                    the buffer `out` itself: a lane reads its
 //                                                    fragment of aux, then writes the same one)
+//   POLY     out = y (if out != null); aux = base + c * y   (one term of appnp_poly: c = *coef
+//                                                    read on the device; base = aux, or
+//                                                    (*coef0) * H on the first step, so the
+//                                                    gamma_0 H term needs no pass of its own)
+//   POLY_DOT POLY with base = aux, and dots[slab * n_rows + row] = sum over the slab's columns
+//                                                    of y * H (the row's share of d gamma_k in
+//                                                    appnp_poly_bwd; fp32, fixed order)
+// POLY and POLY_DOT take y unscaled (scale is not read) and exist for fp32 only.
 enum Epi {
-  EPI_FWD = 0, EPI_BWD = 1, EPI_PARTIAL = 2, EPI_FINISH = 3, EPI_ACCUM = 4, EPI_CHEB = 5
+  EPI_FWD = 0, EPI_BWD = 1, EPI_PARTIAL = 2, EPI_FINISH = 3, EPI_ACCUM = 4, EPI_CHEB = 5,
+  EPI_POLY = 6, EPI_POLY_DOT = 7
 };
 
 struct StepArgs {
@@ -65,6 +74,9 @@ struct StepArgs {
   float* rem_dh;           // remainder pass, adjoint: dH's remainder columns (rows x ld_rem_dh)
   int64_t ld_rem_dh;
   float omega;             // CHEB: the step's Chebyshev weight (appnp_solve_weights)
+  const float* coef;       // POLY / POLY_DOT: the step's coefficient, in device memory
+  const float* coef0;      // POLY: non-null on the first step, base = (*coef0) * H
+  float* dots;             // POLY_DOT: [slabs * n_rows] per-(column slab, row) partial dots
 };
 
 // End of row i's entries in the step's CSR (StepArgs::row_end)

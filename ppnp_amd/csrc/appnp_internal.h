@@ -117,6 +117,17 @@ inline const float* remainder_scale(const appnp_graph* g) {
 int pick_vec(int dtype, int64_t f, const int64_t* lds, int n_ld, const void* const* ptrs,
              int n_ptr);
 hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s);
+// launch_step that also reports (slabs_out, nullable) the column slabs it covers the rows with
+// (gridDim.y): the leading extent of StepArgs::dots
+hipError_t launch_step_slabs(int dtype, int epi, int V, const StepArgs& a, hipStream_t s,
+                             int64_t* slabs_out);
+// appnp_poly: dst = (*coef) * src by rows and, with dots, dots[i] = <src[i], h[i]>; *out = the
+// sum of part[0 .. count) in a fixed order; the most slabs launch_step takes for f features
+hipError_t launch_poly_rows(const float* src, int64_t ld_src, float* dst, int64_t ld_dst,
+                            const float* h, int64_t ld_h, float* dots, int64_t n, int64_t f,
+                            const float* coef, hipStream_t s);
+hipError_t launch_poly_reduce(const float* part, int64_t count, float* out, hipStream_t s);
+int64_t poly_max_slabs(int64_t f);
 hipError_t launch_scale_rows(int dtype, const void* src, int64_t ld_src, void* dst,
                              int64_t ld_dst, int64_t n, int64_t f, float alpha, hipStream_t s);
 
@@ -192,6 +203,52 @@ class DeviceScratch {
   void* ptrs_[kMax];
   int n_ = 0;
 };
+
+// One launch (or copy) on `s` between the kernel timer's two events, tagged `kind` (APPNP_KT_*).
+// Every launch of the propagation entry points (appnp_capi.hip, appnp_poly.hip) goes through
+// here; `launch` returns its hipError_t.
+template <typename Launch>
+inline int timed(hipStream_t s, int kind, Launch launch) {
+  ktimer_begin(s);
+  const int rc = dev_err(launch());
+  ktimer_mark(s, kind);
+  return rc;
+}
+
+// The step arguments every propagation on the held rows of `g` starts from.
+inline StepArgs base_args(const appnp_graph* g, int64_t f, float alpha) {
+  StepArgs a{};
+  a.row_ptr = g->row_ptr;
+  a.col = g->col;
+  a.val = g->val;
+  a.n_rows = g->row_hi - g->row_lo;
+  a.nnz = g->nnz_hat;
+  a.nnz_rows = g->nnz_hat;  // a step over part of the rows' entries overrides nnz only
+  a.zin_rows = g->n;
+  a.row_lo = g->row_lo;
+  a.f = (int32_t)f;
+  a.scale = 1.0f - alpha;
+  a.alpha = alpha;
+  a.drop_scale = 1.0f;
+  a.heavy = g->heavy;
+  a.n_heavy = g->n_heavy;
+  a.heavy_thr = kHeavyRow;
+  a.hub = g->hub;
+  a.n_hub = g->n_hub;
+  return a;
+}
+
+// A_hat^T for the adjoints of a graph whose A_hat is not symmetric: the transposed CSR built at
+// creation (APPNP_GRAPH_TRANSPOSE) and its heavy / hub rows
+inline void use_transpose(StepArgs& a, const appnp_graph* g) {
+  a.row_ptr = g->t_row_ptr;
+  a.col = g->t_col;
+  a.val = g->t_val;
+  a.heavy = g->t_heavy;
+  a.n_heavy = g->t_n_heavy;
+  a.hub = g->t_hub;
+  a.n_hub = g->t_n_hub;
+}
 
 inline int launch_err() { return hipGetLastError() == hipSuccess ? APPNP_OK : APPNP_EDEVICE; }
 

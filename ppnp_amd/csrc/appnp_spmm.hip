@@ -119,10 +119,33 @@ __device__ __forceinline__ void frag_store(T* p, const float (&x)[V], int rem, b
   }
 }
 
+// Returns the lane's share of the row's dot product (POLY_DOT), else 0.
 template <typename T, int V, int EPI, bool TAIL>
-__device__ __forceinline__ void epilogue(const StepArgs& a, int64_t row, int col0,
-                                         const float (&acc)[V], const float (&hv)[V],
-                                         const float (&pv)[V], int rem) {
+__device__ __forceinline__ float epilogue(const StepArgs& a, int64_t row, int col0,
+                                          const float (&acc)[V], const float (&hv)[V],
+                                          const float (&pv)[V], int rem) {
+  if constexpr (EPI == EPI_POLY || EPI == EPI_POLY_DOT) {
+    if (a.out) frag_store<T, V, TAIL>(static_cast<T*>(a.out) + row * a.ld_out + col0, acc, rem);
+    const float c = *a.coef;
+    float dv[V];
+    if (EPI == EPI_POLY && a.coef0) {
+      const float c0 = *a.coef0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) dv[v] = fmaf(c, acc[v], c0 * hv[v]);
+    } else {
+#pragma unroll
+      for (int v = 0; v < V; ++v) dv[v] = fmaf(c, acc[v], pv[v]);
+    }
+    frag_store<T, V, TAIL>(static_cast<T*>(a.aux) + row * a.ld_aux + col0, dv, rem);
+    float dot = 0.0f;
+    if constexpr (EPI == EPI_POLY_DOT) {
+      // a tail lane's slots past rem hold padding (of y and of H): only the valid columns count
+#pragma unroll
+      for (int v = 0; v < V; ++v)
+        if (!TAIL || v < rem) dot = fmaf(acc[v], hv[v], dot);
+    }
+    return dot;
+  }
   float y[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) y[v] = a.scale * acc[v];
@@ -154,6 +177,18 @@ __device__ __forceinline__ void epilogue(const StepArgs& a, int64_t row, int col
     for (int v = 0; v < V; ++v) y[v] = fmaf(a.alpha, hv[v], y[v] + pv[v]);
     frag_store<T, V, TAIL>(static_cast<T*>(a.out) + row * a.ld_out + col0, y, rem);
   }
+  return 0.0f;
+}
+
+// The row's dot product from its lanes' shares (POLY_DOT): a butterfly over the G lanes of the
+// row slab, in a fixed order, then one store per (column slab, row).  Called by every lane that
+// works on the row, with 0 from lanes that hold no valid column: the xor offsets stay below G,
+// so a lane reads only lanes of its own row, all of which are here.
+template <int G>
+__device__ __forceinline__ void store_row_dot(const StepArgs& a, int64_t row, int gl, float dot) {
+#pragma unroll
+  for (int off = 1; off < G; off <<= 1) dot += __shfl_xor(dot, off);
+  if (gl == 0) a.dots[(int64_t)blockIdx.y * a.n_rows + row] = dot;
 }
 
 // The row's epilogue operands, loaded when the row starts so their latency hides under the
@@ -163,6 +198,19 @@ __device__ __forceinline__ void epilogue(const StepArgs& a, int64_t row, int col
 template <typename T, int V, int EPI, bool TAIL>
 __device__ __forceinline__ void load_h(const StepArgs& a, int64_t row, int col0, float (&hv)[V],
                                        float (&pv)[V], int rem) {
+  if constexpr (EPI == EPI_POLY || EPI == EPI_POLY_DOT) {
+    // POLY: H on the first step (base = c0 H), else the sum so far; POLY_DOT: both
+    const bool first = EPI == EPI_POLY && a.coef0 != nullptr;
+#pragma unroll
+    for (int v = 0; v < V; ++v) hv[v] = pv[v] = 0.0f;
+    if (first || EPI == EPI_POLY_DOT)
+      frag_load<T, V, TAIL>(static_cast<const T*>(a.h) + row * a.ld_h + col0, hv, rem,
+                            row + 1 < a.n_rows);
+    if (!first)
+      frag_load<T, V, TAIL>(static_cast<const T*>(a.aux) + row * a.ld_aux + col0, pv, rem,
+                            row + 1 < a.n_rows);
+    return;
+  }
   if constexpr (EPI == EPI_FWD || EPI == EPI_FINISH || EPI == EPI_CHEB) {
     frag_load<T, V, TAIL>(static_cast<const T*>(a.h) + row * a.ld_h + col0, hv, rem,
                           row + 1 < a.n_rows, a.nt & 2);
@@ -253,7 +301,10 @@ __device__ __forceinline__ void wave_row(const StepArgs& a, int64_t row, int lan
 #pragma unroll
     for (int v = 0; v < V; ++v) acc[v] += __shfl_xor(acc[v], off);
   }
-  if (sub == 0 && fact) epilogue<T, V, EPI, TAIL>(a, row, col0, acc, hv, pv, rem);
+  float dot = 0.0f;
+  if (sub == 0 && fact) dot = epilogue<T, V, EPI, TAIL>(a, row, col0, acc, hv, pv, rem);
+  // outside the branch: the whole wave is here, lanes 0 .. G-1 hold the row's shares
+  if constexpr (EPI == EPI_POLY_DOT) store_row_dot<G>(a, row, lane, dot);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -359,7 +410,10 @@ __global__ __launch_bounds__(kBlock) void k_step_narrow(StepArgs a) {
         for (int v = 0; v < V; ++v) acc[v] = fmaf(w[u], z[u][v], acc[v]);
       }
     }
-    if (fact) epilogue<T, V, EPI, TAIL>(a, row, col0, acc, hv, pv, rem);
+    float dot = 0.0f;
+    if (fact) dot = epilogue<T, V, EPI, TAIL>(a, row, col0, acc, hv, pv, rem);
+    // outside the branch: all G lanes of the row are here (they share row, beg and end)
+    if constexpr (EPI == EPI_POLY_DOT) store_row_dot<G>(a, row, gl, dot);
   }
 }
 
@@ -448,8 +502,14 @@ int pick_vec(int dtype, int64_t f, const int64_t* lds, int n_ld, const void* con
   return v;
 }
 
-hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a_in, hipStream_t s) {
+hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s) {
+  return launch_step_slabs(dtype, epi, V, a, s, nullptr);
+}
+
+hipError_t launch_step_slabs(int dtype, int epi, int V, const StepArgs& a_in, hipStream_t s,
+                             int64_t* slabs_out) {
   StepArgs a = a_in;
+  if (slabs_out) *slabs_out = 0;
   if (a.n_rows <= 0 || a.f <= 0) return hipSuccess;
   // lanes per row slab: smallest power of two covering min(F, 64V) features
   auto lanes_for = [&](int v) {
@@ -507,6 +567,7 @@ hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a_in, hipStrea
     a.n_heavy = 0;
   }
   const dim3 grid((unsigned)blocks, (unsigned)slabs);
+  if (slabs_out) *slabs_out = slabs;
   // entries in flight per sub-group of the wide kernel (tools/sweep_uw_bw.sh,
   // tools/sweep_uw.sh).  Bandwidth regime with long rows (>= kWideAvgRow on average): 2 --
   // products-synth fp32 F = 96 8.20 -> 7.32 ms, F = 100 9.76 -> 9.57, products-powerlaw
@@ -541,6 +602,8 @@ hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a_in, hipStrea
       case EPI_FINISH: return launch_v<float, EPI_FINISH>(V, G, wide, uw, un, grid, a, s);
       case EPI_ACCUM: return launch_v<float, EPI_ACCUM>(V, G, wide, uw, un, grid, a, s);
       case EPI_CHEB: return launch_v<float, EPI_CHEB>(V, G, wide, uw, un, grid, a, s);
+      case EPI_POLY: return launch_v<float, EPI_POLY>(V, G, wide, uw, un, grid, a, s);
+      case EPI_POLY_DOT: return launch_v<float, EPI_POLY_DOT>(V, G, wide, uw, un, grid, a, s);
     }
   } else {
     switch (epi) {
@@ -585,5 +648,88 @@ hipError_t launch_scale_rows(int dtype, const void* src, int64_t ld_src, void* d
                        ld_dst, n, f, alpha);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// appnp_poly helpers (fp32).  k_poly_rows: dst[i, :f] = (*coef) * src[i, :f], the gamma_0 term
+// (Z = gamma_0 H at K = 0; dH = gamma_0 dZ), and with `dots` the row dots
+// dots[i] = sum_c src[i, c] * h[i, c] (d gamma_0).  A wavefront per row: lane l takes columns
+// l, l + 64, ... in ascending order, then a butterfly over the 64 lanes -- a fixed order.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_poly_rows(const float* __restrict__ src,
+                                                      int64_t ld_src, float* __restrict__ dst,
+                                                      int64_t ld_dst, const float* __restrict__ h,
+                                                      int64_t ld_h, float* __restrict__ dots,
+                                                      int64_t n, int64_t f,
+                                                      const float* __restrict__ coef) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x >> 6;
+  const float c = *coef;
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wave; r < n; r += nwaves) {
+    float dot = 0.0f;
+    for (int64_t j = lane; j < f; j += kWave) {
+      const float x = src[r * ld_src + j];
+      dst[r * ld_dst + j] = c * x;
+      if (dots) dot = fmaf(x, h[r * ld_h + j], dot);
+    }
+    if (dots) {  // wave-uniform: r and dots are
+#pragma unroll
+      for (int off = 1; off < kWave; off <<= 1) dot += __shfl_xor(dot, off);
+      if (lane == 0) dots[r] = dot;
+    }
+  }
+}
+
+hipError_t launch_poly_rows(const float* src, int64_t ld_src, float* dst, int64_t ld_dst,
+                            const float* h, int64_t ld_h, float* dots, int64_t n, int64_t f,
+                            const float* coef, hipStream_t s) {
+  if (n <= 0 || f <= 0) return hipSuccess;
+  const int64_t blocks = std::min<int64_t>((n + kWavesPerBlock - 1) / kWavesPerBlock, 1 << 16);
+  hipLaunchKernelGGL(k_poly_rows, dim3((unsigned)blocks), dim3(kBlock), 0, s, src, ld_src, dst,
+                     ld_dst, h, ld_h, dots, n, f, coef);
+  return hipGetLastError();
+}
+
+// *out = sum of part[0 .. count): one workgroup of a fixed shape.  Thread t adds elements
+// t, t + 1024, ... in fp64 (in eight interleaved chains), then the 1024 sums meet in a fixed
+// halving tree in LDS.  No atomics; the same bits for the same partials.
+constexpr int kReduceThreads = 1024;
+
+__global__ __launch_bounds__(kReduceThreads) void k_poly_reduce(const float* __restrict__ part,
+                                                                int64_t count,
+                                                                float* __restrict__ out) {
+  __shared__ double tree[kReduceThreads];
+  // eight chains per thread (elements t + 1024 (8 m + j) go to chain j), so eight loads are in
+  // flight instead of one; the chains meet pairwise.  Still one fixed order.
+  constexpr int C = 8;
+  double s[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) s[j] = 0.0;
+  int64_t i = threadIdx.x;
+  for (; i + (C - 1) * kReduceThreads < count; i += C * kReduceThreads) {
+#pragma unroll
+    for (int j = 0; j < C; ++j) s[j] += (double)part[i + j * kReduceThreads];
+  }
+#pragma unroll
+  for (int j = 0; j < C - 1; ++j) {  // the last, partial round
+    if (i + j * kReduceThreads < count) s[j] += (double)part[i + j * kReduceThreads];
+  }
+  tree[threadIdx.x] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  __syncthreads();
+  for (int half = kReduceThreads / 2; half > 0; half >>= 1) {
+    if ((int)threadIdx.x < half) tree[threadIdx.x] += tree[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = (float)tree[0];
+}
+
+hipError_t launch_poly_reduce(const float* part, int64_t count, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_poly_reduce, dim3(1), dim3(kReduceThreads), 0, s, part, count, out);
+  return hipGetLastError();
+}
+
+// Column slabs launch_step gives rows of f features at vector width 1, the most it ever takes:
+// the size of StepArgs::dots per row
+int64_t poly_max_slabs(int64_t f) { return (f + kWave - 1) / kWave; }
 
 }  // namespace appnp

@@ -4,6 +4,8 @@ Mirrors /root/reference/model.py:
   CustomLinear  model.py:13-38   (weight laid out (in, out), fan_out Kaiming init, addmm)
   PPNP          model.py:41-67   (dense precomputed PPR; kept unchanged for callers that pass
                                   ``ppr=``, e.g. batch-main.py:140-146)
+  GPRGNN        new              APPNP whose series coefficients gamma_k are a (trainable) device
+                                  tensor: Z = sum_k gamma_k A_hat^k H on the same kernels.
   APPNP         new              same constructor/forward/get_norm surface as PPNP, but the
                                   propagation ``ppr[idx] @ H`` (model.py:63) is computed as
                                   Z_K[idx] by K fused HIP SpMM launches over A_hat built on
@@ -19,7 +21,7 @@ import torch
 from torch import nn
 
 from .graph import Graph
-from .ops import propagate, solve
+from .ops import heat_coefficients, poly, ppr_coefficients, propagate, solve
 from .ppr import SparsePPR
 from .sparse import SparseFeatures, sparse_linear
 
@@ -260,3 +262,39 @@ class APPNP(nn.Module):
             return _ppr_product(ppr, _encode(self.encoder, X, self.training))
         else:
             raise Exception()
+
+
+class GPRGNN(APPNP):
+    """APPNP with a learnable filter: ``forward(X, idx)`` returns
+    ``poly(graph, encoder(X), coef)[idx]``, Z = sum_{k<=K} coef[k] A_hat^k H (ops.poly), with the
+    encoder, ``get_norm`` and ``SparseFeatures`` input handling of ``APPNP``.
+
+    ``init``: "ppr" (``ppr_coefficients(K, alpha)``: the model starts as APPNP(K, alpha)), "heat"
+    (``heat_coefficients(K, heat_t)``) or a tensor of K + 1 values.  ``coef`` is an
+    ``nn.Parameter`` with ``learn_coef`` (GPR-GNN: negative, high-pass coefficients included) and
+    a buffer otherwise; either way it lives on the device and is never read back.  It is not part
+    of ``get_norm``: the L2 term stays on the first layer.  fp32, no edge dropout (ops.poly)."""
+
+    def __init__(self, n_features, n_classes, adj, K=10, alpha=0.1, init="ppr", learn_coef=True,
+                 heat_t=1.0, hidden_dim=64, drop_prob=0.5, bias=False, mode="sym"):
+        super().__init__(n_features, n_classes, adj, alpha=alpha, K=K, hidden_dim=hidden_dim,
+                         drop_prob=drop_prob, bias=bias, mode=mode)
+        if torch.is_tensor(init):
+            coef = init.detach().to(torch.float32).reshape(-1).clone()
+            if coef.numel() != self.K + 1:
+                raise ValueError(f"init must hold K + 1 = {self.K + 1} coefficients, "
+                                 f"got {coef.numel()}")
+        elif init == "ppr":
+            coef = ppr_coefficients(self.K, self.alpha)
+        elif init == "heat":
+            coef = heat_coefficients(self.K, heat_t)
+        else:
+            raise ValueError(f'init must be "ppr", "heat" or a tensor, got {init!r}')
+        self.learn_coef = bool(learn_coef)
+        if self.learn_coef:
+            self.coef = nn.Parameter(coef)
+        else:
+            self.register_buffer("coef", coef)
+
+    def propagate(self, H):
+        return poly(self.graph(), H.float(), self.coef).to(H.dtype)

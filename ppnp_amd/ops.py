@@ -11,6 +11,7 @@ All calls are stream-ordered on ``torch.cuda.current_stream()``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -230,6 +231,142 @@ def solve(graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
     Chebyshev steps unless ``iters`` is given.  fp32 H on an undirected graph."""
     m = solve_iterations(alpha, tol) if iters is None else int(iters)
     return torch.ops.ppnp_amd.solve(H, graph.key, m, float(alpha))
+
+
+# ---- polynomial propagation with device coefficients (appnp_poly) --------------------------
+
+POLY_MAX_K = 1024  # APPNP_POLY_MAX_K of include/ppnp_amd.h
+
+
+def ppr_coefficients(K: int, alpha: float, device=None) -> torch.Tensor:
+    """gamma of the K-step APPNP series, fp32 [K + 1]: alpha (1-alpha)^k for k < K and
+    (1-alpha)^K last (they sum to 1), so ``poly(graph, H, gamma) == propagate(graph, H, K, alpha)``
+    up to rounding.  Computed in fp64."""
+    K, alpha = int(K), float(alpha)
+    g = torch.tensor([alpha * (1.0 - alpha) ** k for k in range(K)] + [(1.0 - alpha) ** K],
+                     dtype=torch.float64).float()
+    return g.to(device) if device is not None else g
+
+
+def heat_coefficients(K: int, t: float, device=None) -> torch.Tensor:
+    """gamma of heat-kernel diffusion truncated at K, fp32 [K + 1]: e^-t t^k / k!.  Computed in
+    fp64."""
+    k = torch.arange(int(K) + 1, dtype=torch.float64)
+    g = torch.exp(-float(t) + k * math.log(float(t)) - torch.lgamma(k + 1)) if t > 0 else \
+        (k == 0).double()
+    return g.float().to(device) if device is not None else g.float()
+
+
+def _check_coef(coef, graph: Graph) -> int:
+    if not torch.is_tensor(coef) or coef.dtype != torch.float32 or coef.dim() != 1:
+        raise TypeError("coef must be a 1-D float32 tensor [K + 1]")
+    if coef.device != graph.device:
+        raise ValueError(f"coef is on {coef.device}, graph on {graph.device}: the kernels read it "
+                         "in device memory")
+    K = int(coef.numel()) - 1
+    if K < 0 or K > POLY_MAX_K:
+        raise ValueError(f"coef must hold 1 to {POLY_MAX_K + 1} coefficients, got {K + 1}")
+    return K
+
+
+def poly_forward(graph: Graph, H: torch.Tensor, coef: torch.Tensor,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Z = sum_k coef[k] A_hat^k H via ``appnp_poly`` (K = len(coef) - 1 fused HIP launches).
+    ``coef`` stays on the device: nothing is read back.  fp32; see include/ppnp_amd.h."""
+    _check_dense("H", H, graph, graph.n)
+    K = _check_coef(coef, graph)
+    coef = coef.detach().contiguous()
+    Z = torch.empty_like(H, memory_format=torch.contiguous_format) if out is None else out
+    _check_dense("out", Z, graph, graph.n)
+    if Z.dtype != H.dtype or Z.shape != H.shape:
+        raise ValueError("out must match H in shape and dtype")
+    lib = _lib.load()
+    f = int(H.shape[1])
+    ws_bytes = int(lib.appnp_poly_workspace_bytes(graph.handle, f, K, 0))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    with torch.cuda.device(graph.device):
+        rc = lib.appnp_poly(graph.handle, _vp(H), _ld(H), _vp(Z), _ld(Z), f, _DTYPES[H.dtype], K,
+                            _vp(coef), _vp(ws), ws_bytes, _stream(graph.device))
+    _lib.check("appnp_poly", rc)
+    return Z
+
+
+def poly_backward(graph: Graph, dZ: torch.Tensor, H: torch.Tensor | None, coef: torch.Tensor,
+                  need_dcoef: bool = True):
+    """``(dH, dcoef)`` of ``poly_forward`` via ``appnp_poly_bwd``: dH = sum_k coef[k] (A_hat^T)^k dZ
+    and, with ``need_dcoef``, dcoef[k] = <(A_hat^T)^k dZ, H> (fp32 [K + 1] on the device, bitwise
+    reproducible); else dcoef is None and H is not read.  A_hat^T: A_hat itself for 'sym' on an
+    undirected graph, else the transpose built with ``Graph(..., transpose=True)``."""
+    _check_dense("dZ", dZ, graph, graph.n)
+    K = _check_coef(coef, graph)
+    coef = coef.detach().contiguous()
+    if need_dcoef:
+        _check_dense("H", H, graph, graph.n)
+        if H.dtype != dZ.dtype or H.shape != dZ.shape:
+            raise ValueError("H must match dZ in shape and dtype")
+    dH = torch.empty_like(dZ, memory_format=torch.contiguous_format)
+    dcoef = torch.empty(K + 1, dtype=torch.float32, device=graph.device) if need_dcoef else None
+    lib = _lib.load()
+    f = int(dZ.shape[1])
+    ws_bytes = int(lib.appnp_poly_workspace_bytes(graph.handle, f, K, int(bool(need_dcoef))))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    if need_dcoef and dZ.numel() == 0:
+        dcoef.zero_()  # an empty shape: the library has nothing to do
+    with torch.cuda.device(graph.device):
+        rc = lib.appnp_poly_bwd(graph.handle, _vp(dZ), _ld(dZ), _vp(H) if need_dcoef else None,
+                                _ld(H) if need_dcoef else 0, _vp(dH), _ld(dH), _vp(dcoef), f,
+                                _DTYPES[dZ.dtype], K, _vp(coef), _vp(ws), ws_bytes,
+                                _stream(graph.device))
+    _lib.check("appnp_poly_bwd", rc)
+    return dH, dcoef
+
+
+@torch.library.custom_op("ppnp_amd::poly", mutates_args=(), device_types="cuda")
+def _poly_op(H: torch.Tensor, coef: torch.Tensor, graph_key: int) -> torch.Tensor:
+    return poly_forward(Graph.lookup(graph_key), H.contiguous(), coef)
+
+
+@_poly_op.register_fake
+def _(H, coef, graph_key):
+    return torch.empty(H.shape, dtype=H.dtype, device=H.device)
+
+
+@torch.library.custom_op("ppnp_amd::poly_bwd", mutates_args=(), device_types="cuda")
+def _poly_bwd_op(dZ: torch.Tensor, H: torch.Tensor, coef: torch.Tensor, graph_key: int,
+                 need_dcoef: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    dH, dcoef = poly_backward(Graph.lookup(graph_key), dZ.contiguous(), H.contiguous(), coef,
+                              need_dcoef)
+    return dH, dcoef if need_dcoef else coef.new_empty(0)
+
+
+@_poly_bwd_op.register_fake
+def _(dZ, H, coef, graph_key, need_dcoef):
+    return (torch.empty(dZ.shape, dtype=dZ.dtype, device=dZ.device),
+            coef.new_empty(coef.shape if need_dcoef else (0,)))
+
+
+def _poly_setup(ctx, inputs, output):
+    H, coef, ctx.graph_key = inputs
+    ctx.save_for_backward(H, coef)
+
+
+def _poly_grad(ctx, dZ):
+    H, coef = ctx.saved_tensors
+    need = bool(ctx.needs_input_grad[1])
+    dH, dcoef = torch.ops.ppnp_amd.poly_bwd(dZ, H, coef, ctx.graph_key, need)
+    return dH, (dcoef if need else None), None
+
+
+_poly_op.register_autograd(_poly_grad, setup_context=_poly_setup)
+
+
+def poly(graph: Graph, H: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """Differentiable polynomial propagation sum_k coef[k] A_hat^k H (the ``ppnp_amd::poly`` op),
+    with gradients for H and for coef: GPR-GNN when coef is a parameter, APPNP with
+    ``ppr_coefficients``, heat-kernel diffusion with ``heat_coefficients``.  ``coef``: fp32
+    [K + 1] on the graph's device."""
+    _check_coef(coef, graph)
+    return torch.ops.ppnp_amd.poly(H, coef, graph.key)
 
 
 # ---- sparse top-k PPR rows: the column selection (appnp_topk_columns) ----------------------

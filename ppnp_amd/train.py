@@ -10,7 +10,9 @@ Reproduces the call pattern of /root/reference/main.py:63-175:
 * three forwards per epoch (main.py:121, 138, 145)
 * SimpleEarlyStopping with patience 100 (helpers.py:19-55)
 
-The model is ``ppnp_amd.APPNP`` (the dense ``ppnp_amd.PPNP`` with ``--model ppnp``), so the
+The model is ``ppnp_amd.APPNP`` (the dense ``ppnp_amd.PPNP`` with ``--model ppnp``; with
+``--model gprgnn`` ``ppnp_amd.GPRGNN``, whose series coefficients are trained with the weights and
+are not part of the L2 term), so the
 propagation of every forward and backward runs on the fused HIP kernels.  The splitting,
 seeding and early stopping are host bookkeeping, restated so that the harness runs without
 the reference; tests/test_train.py pins them to the reference's own outputs.
@@ -159,7 +161,7 @@ def load_dataset(name):
 
 # -- main.py:71-165 -------------------------------------------------------------------------
 def run_once(adj, attr, labels, args, device, stats=None):
-    from .model import APPNP, PPNP
+    from .model import APPNP, GPRGNN, PPNP
 
     idx_split_args = {"ntrain_per_class": args.ntrain_per_class, "nstopping": args.nstopping,
                       "nknown": args.nknown, "seed": gen_seeds()}
@@ -182,6 +184,10 @@ def run_once(adj, attr, labels, args, device, stats=None):
     if args.model == "ppnp":
         ppr = torch.FloatTensor(_dense_ppr(adj, args.alpha))
         model = PPNP(n_features=X.shape[1], n_classes=n_classes, ppr=ppr).to(device)
+    elif args.model == "gprgnn":
+        model = GPRGNN(n_features=X.shape[1], n_classes=n_classes, adj=adj, K=args.K,
+                       alpha=args.alpha, init=args.coef_init, heat_t=args.heat_t,
+                       learn_coef=not args.fixed_coef).to(device)
     else:
         model = APPNP(n_features=X.shape[1], n_classes=n_classes, adj=adj, alpha=args.alpha,
                       K=args.K, edge_drop=args.edge_drop,
@@ -218,6 +224,8 @@ def run_once(adj, attr, labels, args, device, stats=None):
         if early_stopping.should_stop(acc=float(stop_acc), loss=float(stop_loss), epoch=epoch,
                                       record=record):
             break
+    if stats is not None and args.model == "gprgnn":
+        stats["coef"] = [float(c) for c in model.coef.detach().cpu()]  # gamma when training ended
     return early_stopping.record
 
 
@@ -310,7 +318,13 @@ def parse_args(argv=None):
                    help="--model appnp: propagate with the exact PPNP solver (K is ignored)")
     p.add_argument("--tol", type=float, default=1e-6,
                    help="relative tolerance of --exact")
-    p.add_argument("--model", default="appnp", choices=["appnp", "ppnp"])
+    p.add_argument("--model", default="appnp", choices=["appnp", "ppnp", "gprgnn"])
+    p.add_argument("--coef-init", default="ppr", choices=["ppr", "heat"],
+                   help="--model gprgnn: the coefficients gamma_k start as the APPNP series of "
+                        "--K and --alpha, or as heat-kernel diffusion e^-t t^k / k! (--heat-t)")
+    p.add_argument("--heat-t", type=float, default=1.0, help="t of --coef-init heat")
+    p.add_argument("--fixed-coef", action="store_true",
+                   help="--model gprgnn: keep gamma fixed (a buffer) instead of training it")
     p.add_argument("--sparse-x", action="store_true",
                    help="keep the attribute matrix as a CSR on the GPU (sparse encoder input)")
     p.add_argument("--batch-size", type=int, default=None,
@@ -334,6 +348,8 @@ def parse_args(argv=None):
     p.add_argument("--test", action="store_true")
     p.add_argument("--verbose", action="store_true")
     args = p.parse_args(argv)
+    if args.model == "gprgnn" and (args.edge_drop > 0 or args.exact):
+        p.error("--model gprgnn takes neither --edge-drop nor --exact")
     if args.batch_size is not None:
         if args.batch_size < 1 or not args.ppr_topk or args.ppr_topk < 1:
             p.error("--batch-size needs a positive value and a positive --ppr-topk")
@@ -368,11 +384,13 @@ def main(argv=None):
     set_seeds(args.seed)
     device = torch.device("cuda")
     adj, attr, labels = load_dataset(args.dataset)
-    records, builds = [], []
+    records, builds, coefs = [], [], []
     for _ in range(args.n_runs):
         stats = {}
         rec = run_once(adj, attr, labels, args, device, stats)
         builds.append(stats.get("ppr_build", 0.0))
+        if "coef" in stats:
+            coefs.append(stats["coef"])
         print(rec, flush=True)
         records.append(rec)
     acc = np.array([r["valid_acc"] for r in records])
@@ -381,6 +399,9 @@ def main(argv=None):
                if len(acc) > 1 else 0.0,
                "epochs_mean": float(np.mean([r["epoch"] for r in records])),
                "elapsed_mean": float(np.mean([r["elapsed"] for r in records]))}
+    if coefs:
+        summary.update({"coef_init": args.coef_init, "learn_coef": not args.fixed_coef,
+                        "coef": coefs})
     if args.batch_size:
         if args.ppr_eps is not None:
             summary["ppr_eps"] = args.ppr_eps
