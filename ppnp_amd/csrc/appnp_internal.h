@@ -131,6 +131,13 @@ int64_t poly_max_slabs(int64_t f);
 hipError_t launch_scale_rows(int dtype, const void* src, int64_t ld_src, void* dst,
                              int64_t ld_dst, int64_t n, int64_t f, float alpha, hipStream_t s);
 
+// appnp_propagate.hip: what the whole-graph calls share with the step API of appnp_capi.hip.
+// set_drop: iteration k's dropout parameters.  vec16: whether every operand allows 16-B vectors.
+// remainder_cols: the columns the split layout gives to the remainder pass, 0 for whole rows.
+void set_drop(StepArgs& a, float p_drop, uint64_t seed, int k);
+bool vec16(const int64_t* lds, int n_ld, const void* const* ptrs, int n_ptr);
+int64_t remainder_cols(const appnp_graph* g, int64_t f, int dtype, bool aligned);
+
 // appnp_capi.hip: a tuning override (measurement only, tools/): `name` is read from the
 // environment when APPNP_TUNING=1, else dflt.  Each is read once, at its first use; every name
 // must be listed in kTuningNames (appnp_capi.hip), which appnp_tuning_overrides reports.
@@ -155,9 +162,9 @@ inline unsigned blocks_for(int64_t n) {
 
 // hipError_t -> APPNP_E*, two ways.  build_err is the set-up builders' (graph, blocks, ingest):
 // they check their arguments before the first HIP call, so whatever is not an allocation failure
-// is the device's.  dev_err is the entry points' (appnp_capi.hip, appnp_dist.hip), which hand
-// caller-supplied sizes and pointers to the runtime: there hipErrorInvalidValue is the caller's
-// mistake, APPNP_EINVAL.
+// is the device's.  dev_err is the entry points' (appnp_capi.hip, appnp_propagate.hip,
+// appnp_dist.hip), which hand caller-supplied sizes and pointers to the runtime: there
+// hipErrorInvalidValue is the caller's mistake, APPNP_EINVAL.
 inline int build_err(hipError_t e) {
   if (e == hipSuccess) return APPNP_OK;
   return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? APPNP_ENOMEM : APPNP_EDEVICE;
@@ -205,7 +212,7 @@ class DeviceScratch {
 };
 
 // One launch (or copy) on `s` between the kernel timer's two events, tagged `kind` (APPNP_KT_*).
-// Every launch of the propagation entry points (appnp_capi.hip, appnp_poly.hip) goes through
+// Every launch of the propagation entry points (appnp_propagate.hip, appnp_capi.hip) goes through
 // here; `launch` returns its hipError_t.
 template <typename Launch>
 inline int timed(hipStream_t s, int kind, Launch launch) {
@@ -214,6 +221,61 @@ inline int timed(hipStream_t s, int kind, Launch launch) {
   ktimer_mark(s, kind);
   return rc;
 }
+
+inline int timed_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s,
+                      int kind = APPNP_KT_STEP) {
+  return timed(s, kind, [&] { return launch_step(dtype, epi, V, a, s); });
+}
+
+inline int64_t elem_size(int dtype) { return dtype == APPNP_F32 ? 4 : 2; }
+
+inline bool valid_dtype(int dtype) { return dtype == APPNP_F32 || dtype == APPNP_BF16; }
+
+// Whether an adjoint on `g` needs the transposed CSR built at creation (APPNP_GRAPH_TRANSPOSE):
+// always, except for 'sym' on an undirected graph, whose A_hat is its own transpose.
+inline bool needs_transpose(const appnp_graph* g) {
+  return !(g->mode == APPNP_NORM_SYM && g->symmetric);
+}
+
+// The caller's workspace from its 256-B aligned base on.
+struct Workspace {
+  char* base = nullptr;
+  size_t need = 0;  // the bytes taken from the base
+  size_t room = 0;  // the bytes the workspace holds from the base, `need` included
+
+  // Take `bytes` from the aligned base; APPNP_EINVAL when they are needed and `ws` is null or too
+  // small.  bytes = 0 touches nothing: a caller that needs no workspace may pass none.
+  int take(void* ws, size_t ws_bytes, size_t bytes) {
+    *this = Workspace{};
+    if (bytes == 0) return APPNP_OK;
+    if (!ws) return APPNP_EINVAL;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(ws);
+    const uintptr_t aligned = (p + 255) & ~uintptr_t(255);
+    if (ws_bytes < bytes + (aligned - p)) return APPNP_EINVAL;
+    base = reinterpret_cast<char*>(aligned);
+    need = bytes;
+    room = ws_bytes - (aligned - p);
+    return APPNP_OK;
+  }
+  // the buffer at byte `off` of what was taken, null past its end
+  void* at(size_t off) const { return off < need ? base + off : nullptr; }
+};
+
+// Where a chain of steps stands: what the next step gathers from.
+struct Chain {
+  const void* src;
+  int64_t ld;
+  // the next step reads the source and writes `dst` (null: it keeps no rows), the step after
+  // that reads `dst`
+  void advance(StepArgs& a, void* dst, int64_t ld_dst) {
+    a.zin = src;
+    a.ld_in = ld;
+    a.out = dst;
+    a.ld_out = ld_dst;
+    src = dst;
+    ld = ld_dst;
+  }
+};
 
 // The step arguments every propagation on the held rows of `g` starts from.
 inline StepArgs base_args(const appnp_graph* g, int64_t f, float alpha) {

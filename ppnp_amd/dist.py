@@ -121,7 +121,7 @@ def _avg_lines(row_bytes: int, stride: int) -> float:
 def line_ld(width: int, elem_bytes: int = 4) -> int:
     """Leading dimension (elements) for row gathers: rows padded to start on a 128-B line (next
     power of two up to a line, then whole lines) when that lowers the average lines a row
-    spans; otherwise packed to a 16-B multiple.  Same rule as appnp_capi.hip line_ld."""
+    spans; otherwise packed to a 16-B multiple.  Same rule as appnp_internal.h line_ld."""
     if width <= 0:
         return 1
     line = 128 // elem_bytes

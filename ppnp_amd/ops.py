@@ -46,46 +46,55 @@ def _vp(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
+def _chain_call(fn_name: str, ws_bytes_of, name: str, X: torch.Tensor, graph: Graph, out,
+                build_args) -> torch.Tensor:
+    """One whole-graph propagation call of the library: ``fn_name`` from ``X`` (``name`` in the
+    messages) into ``out``, or into a new contiguous tensor.  ``ws_bytes_of(lib, f, ld, dt)`` sizes
+    the workspace allocated for the call; ``build_args(handle, X, Y, f, dt, ws, ws_bytes, stream)``
+    returns the call's arguments."""
+    _check_dense(name, X, graph, graph.n)
+    Y = torch.empty_like(X, memory_format=torch.contiguous_format) if out is None else out
+    _check_dense("out", Y, graph, graph.n)
+    if Y.dtype != X.dtype or Y.shape != X.shape:
+        raise ValueError(f"out must match {name} in shape and dtype")
+    lib = _lib.load()
+    dt = _DTYPES[X.dtype]
+    f = int(X.shape[1])
+    ws_bytes = int(ws_bytes_of(lib, f, _ld(Y), dt))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
+    with torch.cuda.device(graph.device):
+        rc = getattr(lib, fn_name)(*build_args(graph.handle, X, Y, f, dt, ws, ws_bytes,
+                                               _stream(graph.device)))
+    _lib.check(fn_name, rc)
+    return Y
+
+
+def _chain_ws(graph: Graph, steps: int):
+    """``appnp_workspace_bytes`` for a chain of ``steps`` steps; fewer than two need none."""
+    return lambda lib, f, ld, dt: (lib.appnp_workspace_bytes(graph.handle, f, ld, dt)
+                                   if steps >= 2 else 0)
+
+
+def _chain_args(*params):
+    """The argument order most chain calls share: the operands, ``params``, the workspace."""
+    return lambda g, X, Y, f, dt, ws, ws_bytes, stream: (
+        g, _vp(X), _ld(X), _vp(Y), _ld(Y), f, dt, *params, _vp(ws), ws_bytes, stream)
+
+
 def propagate_forward(graph: Graph, H: torch.Tensor, K: int, alpha: float, p_drop: float = 0.0,
                       seed: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
     """Z = APPNP_K(H) via ``appnp_propagate`` (one fused HIP launch per iteration)."""
-    _check_dense("H", H, graph, graph.n)
-    Z = torch.empty_like(H, memory_format=torch.contiguous_format) if out is None else out
-    _check_dense("out", Z, graph, graph.n)
-    if Z.dtype != H.dtype or Z.shape != H.shape:
-        raise ValueError("out must match H in shape and dtype")
-    lib = _lib.load()
-    dt = _DTYPES[H.dtype]
-    f = int(H.shape[1])
-    ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(Z), dt)) if K >= 2 else 0
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
-    with torch.cuda.device(graph.device):
-        rc = lib.appnp_propagate(graph.handle, _vp(H), _ld(H), _vp(Z), _ld(Z), f, dt, int(K),
-                                 float(alpha), float(p_drop), int(seed) & (2**64 - 1), _vp(ws),
-                                 ws_bytes, _stream(graph.device))
-    _lib.check("appnp_propagate", rc)
-    return Z
+    return _chain_call("appnp_propagate", _chain_ws(graph, K), "H", H, graph, out,
+                       _chain_args(int(K), float(alpha), float(p_drop), int(seed) & (2**64 - 1)))
 
 
 def propagate_backward(graph: Graph, dZ: torch.Tensor, K: int, alpha: float, p_drop: float = 0.0,
                        seed: int = 0) -> torch.Tensor:
     """dH = J^T dZ via ``appnp_propagate_bwd`` (A_hat^T: A_hat itself for 'sym' on an
     undirected graph, else the transpose built with ``Graph(..., transpose=True)``)."""
-    dZ = dZ.contiguous()
-    _check_dense("dZ", dZ, graph, graph.n)
-    dH = torch.empty_like(dZ)
-    lib = _lib.load()
-    dt = _DTYPES[dZ.dtype]
-    f = int(dZ.shape[1])
-    ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(dH), dt)) if K >= 2 else 0
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
-    with torch.cuda.device(graph.device):
-        rc = lib.appnp_propagate_bwd(graph.handle, _vp(dZ), _ld(dZ), _vp(dH), _ld(dH), f, dt,
-                                     int(K), float(alpha), float(p_drop),
-                                     int(seed) & (2**64 - 1), _vp(ws), ws_bytes,
-                                     _stream(graph.device))
-    _lib.check("appnp_propagate_bwd", rc)
-    return dH
+    return _chain_call("appnp_propagate_bwd", _chain_ws(graph, K), "dZ", dZ.contiguous(), graph,
+                       None,
+                       _chain_args(int(K), float(alpha), float(p_drop), int(seed) & (2**64 - 1)))
 
 
 # ---- torch.library registration ---------------------------------------------------------
@@ -159,38 +168,19 @@ def solve_weights(alpha: float, iters: int) -> list[float]:
     return list(w)
 
 
-def _solve_call(name: str, graph: Graph, X: torch.Tensor, iters: int, alpha: float,
-                out: torch.Tensor | None) -> torch.Tensor:
-    _check_dense(name, X, graph, graph.n)
-    Y = torch.empty_like(X, memory_format=torch.contiguous_format) if out is None else out
-    _check_dense("out", Y, graph, graph.n)
-    if Y.dtype != X.dtype or Y.shape != X.shape:
-        raise ValueError(f"out must match {name} in shape and dtype")
-    lib = _lib.load()
-    fn_name = "appnp_solve" if name == "H" else "appnp_solve_bwd"
-    dt = _DTYPES[X.dtype]
-    f = int(X.shape[1])
-    ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(Y), dt)) if iters >= 2 else 0
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
-    with torch.cuda.device(graph.device):
-        rc = getattr(lib, fn_name)(graph.handle, _vp(X), _ld(X), _vp(Y), _ld(Y), f, dt,
-                                   int(iters), float(alpha), _vp(ws), ws_bytes,
-                                   _stream(graph.device))
-    _lib.check(fn_name, rc)
-    return Y
-
-
 def solve_forward(graph: Graph, H: torch.Tensor, iters: int, alpha: float,
                   out: torch.Tensor | None = None) -> torch.Tensor:
     """Z = Pi H after ``iters`` Chebyshev steps via ``appnp_solve`` (one fused HIP launch per
     step).  fp32, undirected graphs, whole rows; see include/ppnp_amd.h."""
-    return _solve_call("H", graph, H, iters, alpha, out)
+    return _chain_call("appnp_solve", _chain_ws(graph, iters), "H", H, graph, out,
+                       _chain_args(int(iters), float(alpha)))
 
 
 def solve_backward(graph: Graph, dZ: torch.Tensor, iters: int, alpha: float) -> torch.Tensor:
     """dH = Pi^T dZ via ``appnp_solve_bwd``: the same solve on A_hat^T, i.e. the gradient of the
     converged operator (rw needs ``Graph(..., transpose=True)``)."""
-    return _solve_call("dZ", graph, dZ.contiguous(), iters, alpha, None)
+    return _chain_call("appnp_solve_bwd", _chain_ws(graph, iters), "dZ", dZ.contiguous(), graph,
+                       None, _chain_args(int(iters), float(alpha)))
 
 
 @torch.library.custom_op("ppnp_amd::solve", mutates_args=(), device_types="cuda")
@@ -273,22 +263,12 @@ def poly_forward(graph: Graph, H: torch.Tensor, coef: torch.Tensor,
                  out: torch.Tensor | None = None) -> torch.Tensor:
     """Z = sum_k coef[k] A_hat^k H via ``appnp_poly`` (K = len(coef) - 1 fused HIP launches).
     ``coef`` stays on the device: nothing is read back.  fp32; see include/ppnp_amd.h."""
-    _check_dense("H", H, graph, graph.n)
+    _check_dense("H", H, graph, graph.n)  # before coef, as ever
     K = _check_coef(coef, graph)
     coef = coef.detach().contiguous()
-    Z = torch.empty_like(H, memory_format=torch.contiguous_format) if out is None else out
-    _check_dense("out", Z, graph, graph.n)
-    if Z.dtype != H.dtype or Z.shape != H.shape:
-        raise ValueError("out must match H in shape and dtype")
-    lib = _lib.load()
-    f = int(H.shape[1])
-    ws_bytes = int(lib.appnp_poly_workspace_bytes(graph.handle, f, K, 0))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
-    with torch.cuda.device(graph.device):
-        rc = lib.appnp_poly(graph.handle, _vp(H), _ld(H), _vp(Z), _ld(Z), f, _DTYPES[H.dtype], K,
-                            _vp(coef), _vp(ws), ws_bytes, _stream(graph.device))
-    _lib.check("appnp_poly", rc)
-    return Z
+    return _chain_call(
+        "appnp_poly", lambda lib, f, ld, dt: lib.appnp_poly_workspace_bytes(graph.handle, f, K, 0),
+        "H", H, graph, out, _chain_args(K, _vp(coef)))
 
 
 def poly_backward(graph: Graph, dZ: torch.Tensor, H: torch.Tensor | None, coef: torch.Tensor,
@@ -304,20 +284,17 @@ def poly_backward(graph: Graph, dZ: torch.Tensor, H: torch.Tensor | None, coef: 
         _check_dense("H", H, graph, graph.n)
         if H.dtype != dZ.dtype or H.shape != dZ.shape:
             raise ValueError("H must match dZ in shape and dtype")
-    dH = torch.empty_like(dZ, memory_format=torch.contiguous_format)
     dcoef = torch.empty(K + 1, dtype=torch.float32, device=graph.device) if need_dcoef else None
-    lib = _lib.load()
-    f = int(dZ.shape[1])
-    ws_bytes = int(lib.appnp_poly_workspace_bytes(graph.handle, f, K, int(bool(need_dcoef))))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=graph.device) if ws_bytes else None
     if need_dcoef and dZ.numel() == 0:
         dcoef.zero_()  # an empty shape: the library has nothing to do
-    with torch.cuda.device(graph.device):
-        rc = lib.appnp_poly_bwd(graph.handle, _vp(dZ), _ld(dZ), _vp(H) if need_dcoef else None,
-                                _ld(H) if need_dcoef else 0, _vp(dH), _ld(dH), _vp(dcoef), f,
-                                _DTYPES[dZ.dtype], K, _vp(coef), _vp(ws), ws_bytes,
-                                _stream(graph.device))
-    _lib.check("appnp_poly_bwd", rc)
+    dH = _chain_call(
+        "appnp_poly_bwd",
+        lambda lib, f, ld, dt: lib.appnp_poly_workspace_bytes(graph.handle, f, K,
+                                                              int(bool(need_dcoef))),
+        "dZ", dZ, graph, None,
+        lambda g, X, Y, f, dt, ws, ws_bytes, stream: (
+            g, _vp(X), _ld(X), _vp(H) if need_dcoef else None, _ld(H) if need_dcoef else 0,
+            _vp(Y), _ld(Y), _vp(dcoef), f, dt, K, _vp(coef), _vp(ws), ws_bytes, stream))
     return dH, dcoef
 
 
@@ -739,6 +716,11 @@ class PropagatePlan:
 
     def __init__(self, graph: Graph, H: torch.Tensor, K: int = 10, alpha: float = 0.1,
                  p_drop: float = 0.0, seed: int = 0):
+        self._capture("appnp_plan_create", graph, H,
+                      (int(K), float(alpha), float(p_drop), int(seed) & (2**64 - 1)))
+
+    def _capture(self, fn_name: str, graph: Graph, H: torch.Tensor, params: tuple):
+        """Allocate Z and the workspace, then record ``fn_name`` on them with ``params``."""
         _check_dense("H", H, graph, graph.n)
         self.graph, self.H = graph, H
         self.Z = torch.empty_like(H, memory_format=torch.contiguous_format)
@@ -750,11 +732,10 @@ class PropagatePlan:
         self._p = C.c_void_p()
         torch.cuda.current_stream(graph.device).synchronize()  # buffers allocated before capture
         with torch.cuda.device(graph.device):
-            rc = lib.appnp_plan_create(graph.handle, _vp(H), _ld(H), _vp(self.Z), _ld(self.Z), f,
-                                       dt, int(K), float(alpha), float(p_drop),
-                                       int(seed) & (2**64 - 1), _vp(self._ws), self._ws_bytes,
+            rc = getattr(lib, fn_name)(graph.handle, _vp(H), _ld(H), _vp(self.Z), _ld(self.Z), f,
+                                       dt, *params, _vp(self._ws), self._ws_bytes,
                                        C.byref(self._p))
-        _lib.check("appnp_plan_create", rc)
+        _lib.check(fn_name, rc)
 
     def __call__(self) -> torch.Tensor:
         with torch.cuda.device(self.graph.device):
@@ -781,22 +762,9 @@ class SolvePlan(PropagatePlan):
 
     def __init__(self, graph: Graph, H: torch.Tensor, alpha: float = 0.1, tol: float = 1e-6,
                  iters: int | None = None):
-        _check_dense("H", H, graph, graph.n)
-        self.graph, self.H = graph, H
+        _check_dense("H", H, graph, graph.n)  # before alpha and tol, as ever
         self.iters = solve_iterations(alpha, tol) if iters is None else int(iters)
-        self.Z = torch.empty_like(H, memory_format=torch.contiguous_format)
-        lib = _lib.load()
-        dt = _DTYPES[H.dtype]
-        f = int(H.shape[1])
-        self._ws_bytes = int(lib.appnp_workspace_bytes(graph.handle, f, _ld(self.Z), dt))
-        self._ws = torch.empty(max(self._ws_bytes, 1), dtype=torch.uint8, device=graph.device)
-        self._p = C.c_void_p()
-        torch.cuda.current_stream(graph.device).synchronize()  # buffers allocated before capture
-        with torch.cuda.device(graph.device):
-            rc = lib.appnp_plan_create_solve(graph.handle, _vp(H), _ld(H), _vp(self.Z),
-                                             _ld(self.Z), f, dt, self.iters, float(alpha),
-                                             _vp(self._ws), self._ws_bytes, C.byref(self._p))
-        _lib.check("appnp_plan_create_solve", rc)
+        self._capture("appnp_plan_create_solve", graph, H, (self.iters, float(alpha)))
 
 
 KERNEL_KINDS = {_lib.KT_COPY: "copy", _lib.KT_STEP: "step", _lib.KT_REM: "rem",

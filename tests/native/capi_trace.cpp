@@ -1,14 +1,15 @@
-// capi_trace.cpp -- the launch trace of ppnp_amd/csrc/appnp_capi.hip, recorded on a CPU.
+// capi_trace.cpp -- the launch trace of ppnp_amd/csrc/appnp_capi.hip and appnp_propagate.hip,
+// recorded on a CPU.
 //
-// appnp_capi.hip holds no kernel: all it does is validate arguments, carve the workspace and
-// request launches from the other units.  This program links the host-only object of that unit
-// against recording stand-ins for the ten internal functions it imports and for the few HIP
-// runtime calls it makes, calls the public entry points on fabricated graphs (every pointer a
-// fixed integer, nothing is dereferenced, no device is touched) and prints each requested launch
-// with every argument, plus each return code.  tests/test_capi_trace.py compares the output with
+// Neither unit holds a kernel: all they do is validate arguments, carve the workspace and
+// request launches from the other units.  This program links their host-only objects against
+// recording stand-ins for the internal functions they import and for the few HIP runtime calls
+// they make, calls the public entry points on fabricated graphs (every pointer a fixed integer,
+// nothing is dereferenced, no device is touched) and prints each requested launch with every
+// argument, plus each return code.  tests/test_capi_trace.py compares the output with
 // tests/golden/capi_trace.txt byte for byte.
 //
-// Run it with every APPNP_* variable removed from the environment (the unit caches overrides).
+// Run it with every APPNP_* variable removed from the environment (the units cache overrides).
 #include <cinttypes>
 #include <cstdio>
 #include <limits>
@@ -34,7 +35,7 @@ void* new_handle() {
 
 }  // namespace
 
-// ---- recording stand-ins: the unit's ten imports ------------------------------------------
+// ---- recording stand-ins: the units' imports ----------------------------------------------
 
 namespace appnp {
 
@@ -106,6 +107,35 @@ hipError_t launch_scale_rows(int dtype, const void* src, int64_t ld_src, void* d
   return hipSuccess;
 }
 
+// the polynomial calls' launches: the step that also reports its column slabs (64 columns each
+// here), the row pass of coef[0] and the reduce of the partial dots
+int64_t poly_max_slabs(int64_t f) { return (f + 63) / 64; }
+
+hipError_t launch_step_slabs(int dtype, int epi, int V, const StepArgs& a, hipStream_t s,
+                             int64_t* slabs_out) {
+  printf("launch_step_slabs dtype=%d epi=%d V=%d s=%#llx coef=%#llx coef0=%#llx dots=%#llx", dtype,
+         epi, V, X(s), X(a.coef), X(a.coef0), X(a.dots));
+  print_args(a);
+  printf("\n");
+  if (slabs_out) *slabs_out = poly_max_slabs(a.f);
+  return hipSuccess;
+}
+
+hipError_t launch_poly_rows(const float* src, int64_t ld_src, float* dst, int64_t ld_dst,
+                            const float* h, int64_t ld_h, float* dots, int64_t n, int64_t f,
+                            const float* coef, hipStream_t s) {
+  printf("launch_poly_rows src=%#llx ld_src=%" PRId64 " dst=%#llx ld_dst=%" PRId64
+         " h=%#llx ld_h=%" PRId64 " dots=%#llx n=%" PRId64 " f=%" PRId64 " coef=%#llx s=%#llx\n",
+         X(src), ld_src, X(dst), ld_dst, X(h), ld_h, X(dots), n, f, X(coef), X(s));
+  return hipSuccess;
+}
+
+hipError_t launch_poly_reduce(const float* part, int64_t count, float* out, hipStream_t s) {
+  printf("launch_poly_reduce part=%#llx count=%" PRId64 " out=%#llx s=%#llx\n", X(part), count,
+         X(out), X(s));
+  return hipSuccess;
+}
+
 int g_build_rc = APPNP_OK;  // what the graph_build* stand-ins return
 
 int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t n,
@@ -141,7 +171,7 @@ void graph_free(appnp_graph*) { printf("graph_free\n"); }
 
 }  // namespace appnp
 
-// ---- recording stand-ins: the HIP runtime calls of the unit --------------------------------
+// ---- recording stand-ins: the HIP runtime calls of the units -------------------------------
 
 hipError_t hipEventCreate(hipEvent_t* e) {
   *e = static_cast<hipEvent_t>(new_handle());
@@ -365,6 +395,36 @@ struct Prop {
       appnp_plan_destroy(p);
     }
     return rc;
+  }
+};
+
+// appnp_poly / appnp_poly_bwd: X, Y are H, Z in the forward and dZ, dH in the adjoint, which
+// reads H (kPartial's address stands in) and writes dcoef where it is not null
+struct Poly {
+  const appnp_graph* g;
+  const void* X = kH;
+  int64_t ld_x;
+  void* Y = kZ;
+  int64_t ld_y;
+  const void* H = kPartial;
+  int64_t ld_h;
+  float* dcoef = at<float>(0x52000000);
+  int64_t f;
+  int dtype = APPNP_F32;
+  int K = 3;
+  const float* coef = at<float>(0x51000000);
+  void* ws = kWs;
+  size_t ws_bytes;
+
+  Poly(const appnp_graph* g_, int64_t f_, int K_ = 3)
+      : g(g_), ld_x(f_), ld_y(f_), ld_h(f_), f(f_), K(K_),
+        ws_bytes(appnp_poly_workspace_bytes(g_, f_, K_, 1)) {}
+  int fwd() const {
+    return appnp_poly(g, X, ld_x, Y, ld_y, f, dtype, K, coef, ws, ws_bytes, kStream);
+  }
+  int bwd() const {
+    return appnp_poly_bwd(g, X, ld_x, H, ld_h, Y, ld_y, dcoef, f, dtype, K, coef, ws, ws_bytes,
+                          kStream);
   }
 };
 
@@ -1111,6 +1171,78 @@ const Case kCases[] = {
     CASE("graph_create_rows: transpose of held rows", appnp_graph* g = nullptr; return appnp_graph_create_rows(at<int32_t>(0x70000000), at<int32_t>(0x71000000), nullptr, 1000, 8000, APPNP_GRAPH_TRANSPOSE, 0, 500, 0, kStream, &g);)
     CASE("graph_create: null indptr", appnp_graph* g = nullptr; return appnp_graph_create(nullptr, at<int32_t>(0x71000000), nullptr, 1000, 8000, 0, kStream, &g);)
     CASE("graph_create: null indices", appnp_graph* g = nullptr; return appnp_graph_create(at<int32_t>(0x70000000), nullptr, nullptr, 1000, 8000, 0, kStream, &g);)
+    // ---- appnp_poly / appnp_poly_bwd -------------------------------------------------------
+    CASE("poly K=0", Poly p(G(0), 64, 0); return p.fwd();)
+    CASE("poly K=1", Poly p(G(0), 64, 1); return p.fwd();)
+    CASE("poly K=1 no ws", Poly p(G(0), 64, 1); p.ws = nullptr; p.ws_bytes = 0; return p.fwd();)
+    CASE("poly K=2", Poly p(G(0), 64, 2); return p.fwd();)
+    CASE("poly K=3", Poly p(G(0), 64); return p.fwd();)
+    CASE("poly K=5", Poly p(G(0), 64, 5); return p.fwd();)
+    CASE("poly F=100 ld=104", Poly p(G(0), 100); p.ld_x = p.ld_y = 104; return p.fwd();)
+    CASE("poly F=7 on a small graph", Poly p(G(G_SMALL), 7); return p.fwd();)
+    CASE("poly rw graph, no transpose", Poly p(G(G_RW | G_ASYM), 64); return p.fwd();)
+    CASE("poly F=100 on a graph with a blocked copy", const appnp_graph* g = G(G_SB4);
+         Poly p(g, 100); const int rc = p.fwd(); print_launches(g); return rc;)
+    CASE("poly unaligned ws", Poly p(G(0), 64); p.ws = off(kWs, 16); return p.fwd();)
+    CASE("poly H not 16-B aligned", Poly p(G(0), 64); p.X = off(kH, 8); return p.fwd();)
+    // two buffers of [200000, 64] fp32
+    CASE("poly unaligned ws, exact size", Poly p(G(0), 64); p.ws = off(kWs, 16); p.ws_bytes = 102400000 + 240; return p.fwd();)
+    CASE("poly: unaligned ws, one byte short", Poly p(G(0), 64); p.ws = off(kWs, 16); p.ws_bytes = 102400000 + 239; return p.fwd();)
+    CASE("poly K=2 one buffer suffices", Poly p(G(0), 64, 2); p.ws_bytes = 51200000; return p.fwd();)
+    CASE("poly: K=3 one buffer is too small", Poly p(G(0), 64); p.ws_bytes = 51200000; return p.fwd();)
+    CASE("poly_bwd K=0", Poly p(G(0), 64, 0); return p.bwd();)
+    CASE("poly_bwd K=0 without dcoef needs no ws", Poly p(G(0), 64, 0); p.dcoef = nullptr; p.ws = nullptr; p.ws_bytes = 0; return p.bwd();)
+    CASE("poly_bwd K=1", Poly p(G(0), 64, 1); return p.bwd();)
+    CASE("poly_bwd K=2", Poly p(G(0), 64, 2); return p.bwd();)
+    CASE("poly_bwd K=3", Poly p(G(0), 64); return p.bwd();)
+    CASE("poly_bwd K=4 F=100", Poly p(G(0), 100, 4); return p.bwd();)
+    CASE("poly_bwd K=3 without dcoef: H is not read", Poly p(G(0), 64); p.dcoef = nullptr; p.ld_h = 63; return p.bwd();)
+    CASE("poly_bwd H with its own leading dimension", Poly p(G(0), 64); p.ld_h = 66; return p.bwd();)
+    CASE("poly_bwd rw graph with transpose", Poly p(G(G_RW | G_TR), 64); return p.bwd();)
+    CASE("poly_bwd sym graph, asymmetric A, with transpose", Poly p(G(G_ASYM | G_TR), 64); return p.bwd();)
+    CASE("poly_bwd sym with a transpose held: A_hat itself", Poly p(G(G_TR), 64, 2); return p.bwd();)
+    CASE("poly_bwd unaligned ws", Poly p(G(0), 64); p.ws = off(kWs, 48); return p.bwd();)
+    // two buffers and one slab of partial dots [200000] fp32
+    CASE("poly_bwd ws exact size", Poly p(G(0), 64); p.ws_bytes = 102400000 + 800000; return p.bwd();)
+    CASE("poly_bwd: ws one byte short", Poly p(G(0), 64); p.ws_bytes = 102400000 + 800000 - 1; return p.bwd();)
+    CASE("poly_bwd: K=0 with dcoef and no ws", Poly p(G(0), 64, 0); p.ws = nullptr; return p.bwd();)
+    CASE("poly: null graph", Poly p(G(0), 64); p.g = nullptr; return p.fwd();)
+    CASE("poly: f < 0", Poly p(G(0), 64); p.f = -1; return p.fwd();)
+    CASE("poly: f > INT32_MAX", Poly p(G(0), 64); p.f = kBig; return p.fwd();)
+    CASE("poly: K < 0", Poly p(G(0), 64); p.K = -1; return p.fwd();)
+    CASE("poly: K too large", Poly p(G(0), 64); p.K = APPNP_POLY_MAX_K + 1; return p.fwd();)
+    CASE("poly: bad dtype", Poly p(G(0), 64); p.dtype = 7; return p.fwd();)
+    CASE("poly: bf16", Poly p(G(0), 64); p.dtype = APPNP_BF16; return p.fwd();)
+    CASE("poly: held rows only", Poly p(G(G_ROWS), 64); return p.fwd();)
+    CASE("poly: held rows and bf16", Poly p(G(G_ROWS), 64); p.dtype = APPNP_BF16; return p.fwd();)
+    CASE("poly: f = 0 is a no-op", Poly p(G(0), 64); p.f = 0; p.X = nullptr; p.coef = nullptr; return p.fwd();)
+    CASE("poly: null H", Poly p(G(0), 64); p.X = nullptr; return p.fwd();)
+    CASE("poly: null Z", Poly p(G(0), 64); p.Y = nullptr; return p.fwd();)
+    CASE("poly: null coef", Poly p(G(0), 64); p.coef = nullptr; return p.fwd();)
+    CASE("poly: ld_h < f", Poly p(G(0), 64); p.ld_x = 63; return p.fwd();)
+    CASE("poly: H == Z", Poly p(G(0), 64); p.Y = kH; return p.fwd();)
+    CASE("poly: K=2 null ws", Poly p(G(0), 64, 2); p.ws = nullptr; return p.fwd();)
+    CASE("poly_bwd: rw without transpose", Poly p(G(G_RW), 64); return p.bwd();)
+    CASE("poly_bwd: sym graph, asymmetric A, no transpose", Poly p(G(G_ASYM), 64); return p.bwd();)
+    CASE("poly_bwd: no transpose and f = 0", Poly p(G(G_RW), 64); p.f = 0; return p.bwd();)
+    CASE("poly_bwd: no transpose and held rows", Poly p(G(G_RW | G_ROWS), 64); return p.bwd();)
+    CASE("poly_bwd: bf16", Poly p(G(0), 64); p.dtype = APPNP_BF16; return p.bwd();)
+    CASE("poly_bwd: null coef", Poly p(G(0), 64); p.coef = nullptr; return p.bwd();)
+    CASE("poly_bwd: dZ == dH", Poly p(G(0), 64); p.Y = kH; return p.bwd();)
+    CASE("poly_bwd: dcoef and null H", Poly p(G(0), 64); p.H = nullptr; return p.bwd();)
+    CASE("poly_bwd: dcoef and ld_h < f", Poly p(G(0), 64); p.ld_h = 63; return p.bwd();)
+    CASE("poly_bwd: dcoef and H == dH", Poly p(G(0), 64); p.H = kZ; return p.bwd();)
+    CASE("poly_workspace_bytes",
+         const appnp_graph* g = G(0); const appnp_graph* rows = G(G_ROWS); const appnp_graph* none = G(G_EMPTY);
+         const int64_t fs_list[] = {-1, 0, 1, 7, 32, 33, 64, 100, 260, kBig};
+         const int ks[] = {-1, 0, 1, 2, 3, 10, APPNP_POLY_MAX_K, APPNP_POLY_MAX_K + 1};
+         for (int64_t f : fs_list) for (int k : ks)
+           printf("f=%" PRId64 " K=%d: %zu %zu held rows %zu %zu\n", f, k, appnp_poly_workspace_bytes(g, f, k, 0),
+                  appnp_poly_workspace_bytes(g, f, k, 1), appnp_poly_workspace_bytes(rows, f, k, 0),
+                  appnp_poly_workspace_bytes(rows, f, k, 1));
+         printf("null graph %zu, no rows %zu\n", appnp_poly_workspace_bytes(nullptr, 64, 3, 1),
+                appnp_poly_workspace_bytes(none, 64, 3, 1));
+         return APPNP_OK;)
 };
 
 }  // namespace

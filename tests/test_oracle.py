@@ -292,7 +292,7 @@ def test_envelope_bounds_two_faithful_chains():
 
 def test_drop_threshold_follows_the_float_abi():
     """p crosses the C ABI as a float: the oracle's threshold is float32(p) * 2^24 (0.3 ->
-    5033165, one more than the double 0.3 gives), matching set_drop in appnp_capi.hip."""
+    5033165, one more than the double 0.3 gives), matching set_drop in appnp_propagate.hip."""
     assert O.drop_threshold(0.3) == 5033165
     assert O.drop_threshold(0.5) == 1 << 23
     assert O.drop_threshold(0.0) == 0
