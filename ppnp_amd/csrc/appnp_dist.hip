@@ -1,29 +1,43 @@
 // appnp_dist.hip -- row-partitioned multi-GPU propagation behind the C ABI
 // (include/ppnp_amd.h appnp_dist_*; SURVEY.md 8(b) "appnp_dist_create").
 //
-// Host orchestration only: every iteration is one or two appnp_step launches on the held rows
-// (appnp_capi.hip), and the row shards travel through the caller's all-gather callback.  The
-// schedule is ppnp_amd/dist.py PartitionedAPPNP.run for a pure row layout:
+// Host orchestration only: every iteration is a few appnp_step* launches on the held rows
+// (appnp_capi.hip), and the row shards travel through the caller's exchange callbacks.  There is
+// one schedule (Schedule::run; ppnp_amd/dist.py PartitionedAPPNP.run for a pure row layout):
 //
-//   Z_0: H's held rows -> buffer 0 at [lo, hi), all-gather (every rank needs all of Z_0)
-//   k = 0 .. K-1:  src = buffer k&1 (all P S rows), dst = buffer (k+1)&1 at [lo, hi)
-//                  -- or Z itself on the last iteration (no exchange follows it)
-//     overlap:     LOCAL  (columns in [lo, hi): own shard, complete)  -> fp32 partial
-//                  wait for the exchange of src (internal stream)
-//                  REMOTE (the other columns) + partial + alpha H      -> dst
-//     otherwise:   ALL                                                -> dst
-//     k < K-1:     exchange dst (overlap: on the internal stream, behind an event on `stream`;
-//                  waited for inside the next iteration)
+//   Z_0: seed iterate 0 with H's held rows, publish it (every rank needs all of Z_0)
+//   k = 0 .. K-1:  iterate k&1 (all P S rows) -> the held rows of iterate (k+1)&1
+//                  -- or Z itself on the last iteration (nothing is published after it)
+//     the early product, on what this rank already holds         -> fp32 partial
+//     wait for the exchange of iterate k&1 (internal stream xs)
+//     the finishing product + partial + alpha H                   -> the held rows
+//     k < K-1:     publish iterate (k+1)&1
 //
-// The two buffers alternate, and each exchange is waited for before its buffer is written
-// again.  So the only concurrent accesses are the exchange of src, which writes the other
-// ranks' shards, and the local-column step, which reads this rank's shard.
+// It varies in two ways, both fixed per call.
 //
-// Split rows (fp32 F = 32q + r, a graph built with a source-blocked copy of the held rows,
-// appnp_step_split): each iterate is kept as two full-height parts, main [P S, 32q] (whole
-// cache lines per gathered row) and remainder [P S, width of the copy]; both are exchanged
-// (two all-gather calls per exchange), the main part runs the SpMM kernel (local / remote with
-// overlap) and the remainder part the persistent L2-blocked pass once the exchange has landed.
+// The layout of an iterate.  Whole rows: one [P S, ld] buffer.  Split rows (fp32 F = 32q + r on
+// a graph with a source-blocked copy of the held rows, appnp_step_split): two full-height
+// parts, main [P S, 32q] (whole cache lines per gathered row) and remainder [P S, width of the
+// copy]; both are exchanged, the main part runs the SpMM kernel and the remainder part the
+// persistent L2-blocked pass, inside the finishing product, once its exchange has landed.
+//
+// The exchange.
+//   in stream order (no overlap): all-gather each part on `stream`; no early product, the
+//     finishing product is ALL.
+//   overlapped: the all-gathers run on xs behind the event `produced` and end in `exchanged`,
+//     which `stream` waits for between the early product LOCAL (columns in [lo, hi): the own
+//     shard, complete) and the finishing product REMOTE.  Z_0 is still exchanged in stream
+//     order, nothing could overlap it; rows without main columns (fs = 0) run ALL.
+//   pipelined (appnp_dist_set_broadcast): one broadcast per row shard on xs, each followed by
+//     its `arrived` event; the early product is FIRST on the own shard, the finishing product
+//     ACC per group of arrived shards and LAST on the last group.  A remainder part is
+//     all-gathered on xs before the broadcasts (it is small and lands first); LAST waits for it.
+//
+// The two iterates alternate, and each exchange is waited for before its buffers are written
+// again.  So the only concurrent accesses are the exchange of the source iterate, which writes
+// the other ranks' shards, and the early product, which reads this rank's shard.
+//
+// tests/test_dist_trace.py pins every launch, record, wait and exchange of this unit on the CPU.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -81,7 +95,7 @@ struct WsLayout {
 
 WsLayout ws_layout(const appnp_dist* d, int64_t f, int dtype) {
   WsLayout w;
-  const int64_t es = dtype == APPNP_F32 ? 4 : 2;
+  const int64_t es = appnp::elem_size(dtype);
   const size_t rows_pad = (size_t)(d->shard * d->nranks);
   w.ld = appnp::line_ld(f, dtype);
   w.buf_bytes = round_up(rows_pad * (size_t)(w.ld * es), kAlign);
@@ -147,21 +161,6 @@ int exchange_on(appnp_dist* d, void* buf, size_t shard_bytes, hipStream_t s) {
   return rc;
 }
 
-// The pipelined exchange of one iterate: xs waits for the producer, then broadcasts row shard r
-// from rank r, r = 0 .. P-1 in turn (the same order on every rank), each bracketed for the timer
-// and followed by its arrival event.
-int exchange_shards(appnp_dist* d, char* full, size_t shard_bytes, hipStream_t s) {
-  int rc = dev_err(hipEventRecord(d->produced, s));
-  if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(d->xs, d->produced, 0));
-  for (int r = 0; r < d->nranks && rc == APPNP_OK; ++r) {
-    appnp::ktimer_begin(d->xs);
-    rc = d->bcast(full + (size_t)r * shard_bytes, shard_bytes, r, d->nranks, d->xs, d->bctx);
-    appnp::ktimer_mark(d->xs, APPNP_KT_XCHG);
-    if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->arrived[r], d->xs));
-  }
-  return rc;
-}
-
 // Groups of remote shards in arrival order (ppnp_amd/dist.py shard_groups): sized 1, 2, 4, ...
 // from the last to arrive backwards, cut where a group would span the own shard, then adjacent
 // groups merged, front first, down to ceil(log2 R) groups.
@@ -202,70 +201,6 @@ std::vector<std::pair<int, int>> shard_groups(int R, int ri) {
   return groups;
 }
 
-bool aligned16(const void* p, int64_t ld) {
-  return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) % 16) == 0;
-}
-
-// The loop of appnp_dist_propagate on the split layout (see the file comment).
-int propagate_split_rows(appnp_dist* d, const WsLayout& w, const float* H, int64_t ld_h, float* Z,
-                         int64_t ld_z, int64_t f, int K, float alpha, float p_drop,
-                         uint64_t seed, char* base, hipStream_t s) {
-  float* mainb[2] = {reinterpret_cast<float*>(base),
-                     reinterpret_cast<float*>(base + w.part_bytes)};
-  float* remb[2] = {reinterpret_cast<float*>(base + w.main_bytes),
-                    reinterpret_cast<float*>(base + w.part_bytes + w.main_bytes)};
-  float* partial = d->overlap ? reinterpret_cast<float*>(base + 2 * w.part_bytes) : nullptr;
-  const size_t main_shard = (size_t)d->shard * (size_t)w.fs * 4;
-  const size_t rem_shard = (size_t)d->shard * (size_t)w.rw * 4;
-  auto exchange = [&](int b, hipStream_t xs) {
-    int rc = APPNP_OK;
-    if (w.fs > 0) rc = exchange_on(d, mainb[b], main_shard, xs);
-    if (rc == APPNP_OK) rc = exchange_on(d, remb[b], rem_shard, xs);
-    return rc;
-  };
-  int rc = appnp_split_copy(d->g, H, ld_h, f, w.fs ? mainb[0] : nullptr, remb[0], s);
-  if (rc == APPNP_OK && d->nranks > 1) rc = exchange(0, s);
-  bool pending = false;
-  for (int k = 0; k < K && rc == APPNP_OK; ++k) {
-    const bool last = k == K - 1;
-    const int cur = k & 1, nxt = cur ^ 1;
-    float* zm_out = last ? nullptr : mainb[nxt];
-    float* zr_out = last ? nullptr : remb[nxt];
-    float* zout = last ? Z : nullptr;
-    if (d->overlap && w.fs > 0) {
-      rc = appnp_step_split(d->g, APPNP_PART_LOCAL, mainb[cur], remb[cur], H, ld_h, zm_out, zr_out,
-                            zout, ld_z, partial, w.fs, f, k, alpha, p_drop, seed, s);
-      if (rc == APPNP_OK && pending) {
-        rc = dev_err(hipStreamWaitEvent(s, d->exchanged, 0));
-        pending = false;
-      }
-      if (rc == APPNP_OK)
-        rc = appnp_step_split(d->g, APPNP_PART_REMOTE, mainb[cur], remb[cur], H, ld_h, zm_out,
-                              zr_out, zout, ld_z, partial, w.fs, f, k, alpha, p_drop, seed, s);
-    } else {
-      if (pending) {
-        rc = dev_err(hipStreamWaitEvent(s, d->exchanged, 0));
-        pending = false;
-      }
-      if (rc == APPNP_OK)
-        rc = appnp_step_split(d->g, APPNP_PART_ALL, mainb[cur], remb[cur], H, ld_h, zm_out,
-                              zr_out, zout, ld_z, nullptr, 0, f, k, alpha, p_drop, seed, s);
-    }
-    if (rc != APPNP_OK || last || d->nranks == 1) continue;
-    if (d->overlap) {
-      rc = dev_err(hipEventRecord(d->produced, s));
-      if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(d->xs, d->produced, 0));
-      if (rc == APPNP_OK) rc = exchange(nxt, d->xs);
-      if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->exchanged, d->xs));
-      pending = rc == APPNP_OK;
-    } else {
-      rc = exchange(nxt, s);
-    }
-  }
-  if (pending) (void)hipStreamWaitEvent(s, d->exchanged, 0);
-  return rc;
-}
-
 // rows x (f elements) between two row-major matrices with leading dimensions in elements
 hipError_t copy_rows(void* dst, int64_t ld_dst, const void* src, int64_t ld_src, int64_t rows,
                      int64_t f, int64_t es, hipStream_t s) {
@@ -274,96 +209,196 @@ hipError_t copy_rows(void* dst, int64_t ld_dst, const void* src, int64_t ld_src,
                           (size_t)(f * es), (size_t)rows, hipMemcpyDeviceToDevice, s);
 }
 
-// appnp_dist_propagate on the split layout with the pipelined exchange: the remainder part is
-// all-gathered first on xs, the main part by one broadcast per shard; the main product runs FIRST
-// on the own shard, ACC per group of arrived shards, LAST on the last group (then the remainder
-// pass, after the remainder part's exchange).
-int propagate_split_rows_pipelined(appnp_dist* d, const WsLayout& w, const float* H, int64_t ld_h,
-                                   float* Z, int64_t ld_z, int64_t f, int K, float alpha,
-                                   float p_drop, uint64_t seed, char* base, hipStream_t s) {
-  float* mainb[2] = {reinterpret_cast<float*>(base),
-                     reinterpret_cast<float*>(base + w.part_bytes)};
-  float* remb[2] = {reinterpret_cast<float*>(base + w.main_bytes),
-                    reinterpret_cast<float*>(base + w.part_bytes + w.main_bytes)};
-  float* partial = reinterpret_cast<float*>(base + 2 * w.part_bytes);
-  const size_t main_shard = (size_t)d->shard * (size_t)w.fs * 4;
-  const size_t rem_shard = (size_t)d->shard * (size_t)w.rw * 4;
-  auto exchange = [&](int b) {
-    // the remainder part first (small: it lands before the main shards), then the main part
-    int rc = dev_err(hipEventRecord(d->produced, s));
-    if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(d->xs, d->produced, 0));
-    if (rc == APPNP_OK) rc = exchange_on(d, remb[b], rem_shard, d->xs);
-    if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->exchanged, d->xs));
-    if (rc == APPNP_OK) rc = exchange_shards(d, reinterpret_cast<char*>(mainb[b]), main_shard, s);
-    return rc;
-  };
-  const int ri = d->rank;
-  int rc = appnp_split_copy(d->g, H, ld_h, f, mainb[0], remb[0], s);
-  if (rc == APPNP_OK) rc = exchange(0);
-  for (int k = 0; k < K && rc == APPNP_OK; ++k) {
-    const bool last = k == K - 1;
+// What a step contributes to the held rows: appnp_part, then appnp_shard_mode
+enum Role {
+  ALL = APPNP_PART_ALL,
+  LOCAL = APPNP_PART_LOCAL,
+  REMOTE = APPNP_PART_REMOTE,
+  FIRST,  // over a range of source shards: FIRST + its appnp_shard_mode
+  ACC = FIRST + APPNP_SHARDS_ACC,
+  LAST = FIRST + APPNP_SHARDS_LAST
+};
+static_assert(APPNP_SHARDS_FIRST == 0 && FIRST > REMOTE, "appnp_part, then appnp_shard_mode");
+// the step writes the output rows (+ alpha H); the others write the partial
+constexpr bool finishes(Role r) { return r == ALL || r == REMOTE || r == LAST; }
+
+// One propagation (see the file comment): the call's operands, where the two iterates and the
+// partial live in the workspace, which parts of an iterate are exchanged and how, and the loop.
+struct Schedule {
+  appnp_dist* d;
+  hipStream_t s;
+  const void* H;
+  int64_t ld_h;
+  void* Z;
+  int64_t ld_z;
+  int64_t f;
+  int dtype, K;
+  float alpha, p_drop;
+  uint64_t seed;
+  // the layout, from WsLayout: iterate b is main[b] (whole rows: all of it, [P S, ld]) and, in
+  // the split layout, rem[b]; *_shard are the bytes of one rank's rows of a part, 0: no such part
+  bool split;
+  int64_t ld, fs;
+  char* main[2];
+  char* rem[2];
+  size_t main_shard, rem_shard;
+  float* partial;  // [S, ld_partial] fp32 (overlap)
+  int64_t ld_partial;
+  bool pipelined;        // the main part travels by broadcasts (d->bcast, which implies overlap and
+                         // so fp32: appnp_dist_propagate rejects bf16 with overlap)
+  bool pending = false;  // an all-gather on xs that `s` has not waited for yet
+
+  // H / Z: set by the caller, which may have staged them
+  Schedule(appnp_dist* d_, const WsLayout& w, bool split_, char* base, int64_t f_, int dtype_,
+           int K_, float alpha_, float p_drop_, uint64_t seed_, hipStream_t s_)
+      : d(d_), s(s_), H(nullptr), ld_h(0), Z(nullptr), ld_z(0), f(f_), dtype(dtype_), K(K_),
+        alpha(alpha_), p_drop(p_drop_), seed(seed_), split(split_), ld(w.ld), fs(w.fs) {
+    const size_t stride = split ? w.part_bytes : w.buf_bytes;
+    for (int b = 0; b < 2; ++b) {
+      main[b] = base + b * stride;
+      rem[b] = split ? main[b] + w.main_bytes : nullptr;
+    }
+    const size_t S = (size_t)d->shard;
+    main_shard = S * (size_t)(split ? fs * 4 : ld * appnp::elem_size(dtype));
+    rem_shard = split ? S * (size_t)w.rw * 4 : 0;
+    partial = d->overlap ? reinterpret_cast<float*>(base + 2 * stride) : nullptr;
+    ld_partial = split ? fs : ld;
+    pipelined = d->bcast && main_shard > 0;
+  }
+
+  static float* f32(char* p) { return reinterpret_cast<float*>(p); }
+  // the held rows of whole-row iterate b
+  char* own(int b) const { return main[b] + (size_t)(d->lo * ld * appnp::elem_size(dtype)); }
+
+  // Z_0's held rows
+  int seed_rows() const {
+    if (split)
+      return appnp_split_copy(d->g, static_cast<const float*>(H), ld_h, f,
+                              fs ? f32(main[0]) : nullptr, f32(rem[0]), s);
+    return dev_err(
+        copy_rows(own(0), ld, H, ld_h, d->hi - d->lo, f, appnp::elem_size(dtype), s));
+  }
+
+  // The step of iteration k in `role` (FIRST / ACC / LAST: over the source shards [s_lo, s_hi)):
+  // from iterate k&1; a finishing step writes the held rows of the other iterate, or Z on the
+  // last iteration.  A step is handed only what its role reads and writes.
+  int step(Role role, int s_lo, int s_hi, int k) const {
+    const bool fin = finishes(role), last = k == K - 1;
     const int cur = k & 1, nxt = cur ^ 1;
-    rc = appnp_step_split_shards(d->g, ri, ri + 1, APPNP_SHARDS_FIRST, mainb[cur], nullptr,
-                                 nullptr, 0, nullptr, nullptr, nullptr, 0, partial, w.fs, f, k,
-                                 alpha, p_drop, seed, s);
+    const float* h = fin ? static_cast<const float*>(H) : nullptr;
+    const int64_t lh = fin ? ld_h : 0;
+    if (split) {
+      const float* zin_rem = fin ? f32(rem[cur]) : nullptr;
+      float* out_main = fin && !last ? f32(main[nxt]) : nullptr;
+      float* out_rem = fin && !last ? f32(rem[nxt]) : nullptr;
+      float* z = fin && last ? static_cast<float*>(Z) : nullptr;
+      const int64_t lz = fin ? ld_z : 0;
+      float* part = role == ALL ? nullptr : partial;
+      const int64_t ld_part = role == ALL ? 0 : ld_partial;
+      if (role < FIRST)
+        return appnp_step_split(d->g, role, f32(main[cur]), zin_rem, h, lh, out_main, out_rem, z,
+                                lz, part, ld_part, f, k, alpha, p_drop, seed, s);
+      return appnp_step_split_shards(d->g, s_lo, s_hi, role - FIRST, f32(main[cur]), zin_rem, h,
+                                     lh, out_main, out_rem, z, lz, part, ld_part, f, k, alpha,
+                                     p_drop, seed, s);
+    }
+    void* out = !fin ? nullptr : last ? Z : own(nxt);
+    const int64_t ld_out = !fin ? 0 : last ? ld_z : ld;
+    if (role >= FIRST)
+      return appnp_step_shards(d->g, s_lo, s_hi, role - FIRST, f32(main[cur]), ld, h, lh,
+                               static_cast<float*>(out), ld_out, partial, ld_partial, f, k, alpha,
+                               p_drop, seed, s);
+    // appnp_step takes LOCAL's partial as its output rows, and another one only to read it
+    const bool reads = role == REMOTE;
+    return appnp_step(d->g, role, main[cur], ld, h, lh, role == LOCAL ? partial : out,
+                      role == LOCAL ? ld_partial : ld_out, reads ? partial : nullptr,
+                      reads ? ld_partial : 0, f, dtype, k, alpha, p_drop, seed, s);
+  }
+
+  // All-gather the parts of iterate b on stream `on`: the main part unless it travels by
+  // broadcasts, then the remainder part
+  int all_gather(int b, hipStream_t on) const {
+    int rc = APPNP_OK;
+    if (main_shard && !pipelined) rc = exchange_on(d, main[b], main_shard, on);
+    if (rc == APPNP_OK && rem_shard) rc = exchange_on(d, rem[b], rem_shard, on);
+    return rc;
+  }
+
+  // xs goes on behind what `s` holds now
+  int xs_follows() const {
+    const int rc = dev_err(hipEventRecord(d->produced, s));
+    return rc == APPNP_OK ? dev_err(hipStreamWaitEvent(d->xs, d->produced, 0)) : rc;
+  }
+
+  // `s` goes on behind the all-gather on xs
+  int wait_exchanged() {
+    pending = false;
+    return dev_err(hipStreamWaitEvent(s, d->exchanged, 0));
+  }
+
+  // Hand the held rows of iterate b, written on `s`, to every rank.  Z_0 (`first`) has nothing to
+  // overlap with, so the all-gather loops exchange it in stream order even with overlap.
+  int publish(int b, bool first) {
+    if (d->nranks == 1) return APPNP_OK;
+    if (!pipelined && (first || !d->overlap)) return all_gather(b, s);
+    int rc = APPNP_OK;
+    if (!pipelined || rem_shard) {
+      // the all-gathered parts on xs; pipelined, that is the remainder part (small: it lands
+      // before the main shards), which LAST waits for -- otherwise the next iteration does
+      rc = xs_follows();
+      if (rc == APPNP_OK) rc = all_gather(b, d->xs);
+      if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->exchanged, d->xs));
+      pending = rc == APPNP_OK && !pipelined;
+    }
+    if (!pipelined) return rc;
+    // row shard r from rank r, r = 0 .. P-1 in turn (the same order on every rank), each bracketed
+    // for the timer and followed by its arrival event
+    if (rc == APPNP_OK) rc = xs_follows();
+    for (int r = 0; r < d->nranks && rc == APPNP_OK; ++r) {
+      appnp::ktimer_begin(d->xs);
+      rc = d->bcast(main[b] + (size_t)r * main_shard, main_shard, r, d->nranks, d->xs, d->bctx);
+      appnp::ktimer_mark(d->xs, APPNP_KT_XCHG);
+      if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->arrived[r], d->xs));
+    }
+    return rc;
+  }
+
+  // The finishing product of iteration k, with the waits it needs
+  int finish(int k, bool early) {
+    int rc = APPNP_OK;
+    if (!pipelined) {
+      if (pending) rc = wait_exchanged();
+      return rc == APPNP_OK ? step(early ? REMOTE : ALL, 0, 0, k) : rc;
+    }
+    // ACC per group of arrived shards, LAST (and with it the remainder pass) on the last group
     for (size_t i = 0; i < d->groups.size() && rc == APPNP_OK; ++i) {
       const int a = d->groups[i].first, b = d->groups[i].second;
+      const bool last_group = i + 1 == d->groups.size();
       rc = dev_err(hipStreamWaitEvent(s, d->arrived[b - 1], 0));
-      if (rc != APPNP_OK) break;
-      if (i + 1 < d->groups.size()) {
-        rc = appnp_step_split_shards(d->g, a, b, APPNP_SHARDS_ACC, mainb[cur], nullptr, nullptr,
-                                     0, nullptr, nullptr, nullptr, 0, partial, w.fs, f, k, alpha,
-                                     p_drop, seed, s);
-        continue;
-      }
-      rc = dev_err(hipStreamWaitEvent(s, d->exchanged, 0));  // the remainder part
-      if (rc == APPNP_OK)
-        rc = appnp_step_split_shards(d->g, a, b, APPNP_SHARDS_LAST, mainb[cur], remb[cur], H,
-                                     ld_h, last ? nullptr : mainb[nxt], last ? nullptr : remb[nxt],
-                                     last ? Z : nullptr, ld_z, partial, w.fs, f, k, alpha, p_drop,
-                                     seed, s);
+      if (rc == APPNP_OK && last_group && rem_shard) rc = wait_exchanged();
+      if (rc == APPNP_OK) rc = step(last_group ? LAST : ACC, a, b, k);
     }
     // the own shard's send: the last thing on xs of this exchange (s waits for it before the
     // next exchange reuses the buffer, at no cost: it precedes that exchange on xs anyway)
     if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(s, d->arrived[d->nranks - 1], 0));
-    if (rc == APPNP_OK && !last) rc = exchange(nxt);
+    return rc;
   }
-  return rc;
-}
 
-// The same for whole rows (appnp_step_shards), the iterate in [P S, ld] buffers.
-int propagate_rows_pipelined(appnp_dist* d, const WsLayout& w, const void* H, int64_t ld_h,
-                             void* Z, int64_t ld_z, int64_t f, int K, float alpha, float p_drop,
-                             uint64_t seed, char* base, hipStream_t s) {
-  char* buf[2] = {base, base + w.buf_bytes};
-  float* partial = reinterpret_cast<float*>(base + w.partial_off);
-  const size_t row_bytes = (size_t)(w.ld * 4);
-  const size_t shard_bytes = (size_t)d->shard * row_bytes;
-  const int64_t rows = d->hi - d->lo;
-  auto own = [&](char* b) { return b + (size_t)d->lo * row_bytes; };
-  const int ri = d->rank;
-  int rc = dev_err(copy_rows(own(buf[0]), w.ld, H, ld_h, rows, f, 4, s));
-  if (rc == APPNP_OK) rc = exchange_shards(d, buf[0], shard_bytes, s);
-  for (int k = 0; k < K && rc == APPNP_OK; ++k) {
-    const bool last = k == K - 1;
-    const float* src = reinterpret_cast<const float*>(buf[k & 1]);
-    float* dst = last ? static_cast<float*>(Z) : reinterpret_cast<float*>(own(buf[(k + 1) & 1]));
-    const int64_t ld_dst = last ? ld_z : w.ld;
-    rc = appnp_step_shards(d->g, ri, ri + 1, APPNP_SHARDS_FIRST, src, w.ld, nullptr, 0, nullptr,
-                           0, partial, w.ld, f, k, alpha, p_drop, seed, s);
-    for (size_t i = 0; i < d->groups.size() && rc == APPNP_OK; ++i) {
-      const int a = d->groups[i].first, b = d->groups[i].second;
-      rc = dev_err(hipStreamWaitEvent(s, d->arrived[b - 1], 0));
-      const int mode = i + 1 < d->groups.size() ? APPNP_SHARDS_ACC : APPNP_SHARDS_LAST;
-      if (rc == APPNP_OK)
-        rc = appnp_step_shards(d->g, a, b, mode, src, w.ld, static_cast<const float*>(H), ld_h,
-                               dst, ld_dst, partial, w.ld, f, k, alpha, p_drop, seed, s);
+  int run() {
+    // the early product needs main columns of its own: LOCAL on the own columns, FIRST on the
+    // own shard
+    const bool early = pipelined || (d->overlap && main_shard > 0);
+    int rc = seed_rows();
+    if (rc == APPNP_OK) rc = publish(0, true);
+    for (int k = 0; k < K && rc == APPNP_OK; ++k) {
+      if (early) rc = step(pipelined ? FIRST : LOCAL, d->rank, d->rank + 1, k);
+      if (rc == APPNP_OK) rc = finish(k, early);
+      if (rc == APPNP_OK && k < K - 1) rc = publish((k + 1) & 1, false);
     }
-    if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(s, d->arrived[d->nranks - 1], 0));
-    if (rc == APPNP_OK && !last) rc = exchange_shards(d, buf[(k + 1) & 1], shard_bytes, s);
+    if (pending) (void)wait_exchanged();  // never leave xs running ahead
+    return rc;
   }
-  return rc;
-}
+};
 
 // RCCL, resolved at first use (appnp_allgather_rccl, appnp_bcast_rccl)
 typedef int (*nccl_allgather_t)(const void*, void*, size_t, int, void*, hipStream_t);
@@ -450,7 +485,7 @@ int appnp_dist_rows(const appnp_dist* d, int64_t* row_lo, int64_t* row_hi, int64
 const appnp_graph* appnp_dist_graph(const appnp_dist* d) { return d ? d->g : nullptr; }
 
 size_t appnp_dist_workspace_bytes(const appnp_dist* d, int64_t f, int dtype) {
-  if (!d || f <= 0 || (dtype != APPNP_F32 && dtype != APPNP_BF16)) return 0;
+  if (!d || f <= 0 || !appnp::valid_dtype(dtype)) return 0;
   const WsLayout w = ws_layout(d, f, dtype);
   return std::max(w.total, w.split_total);
 }
@@ -458,7 +493,7 @@ size_t appnp_dist_workspace_bytes(const appnp_dist* d, int64_t f, int dtype) {
 int appnp_dist_propagate(appnp_dist* d, const void* H, int64_t ld_h, void* Z, int64_t ld_z,
                          int64_t f, int dtype, int K, float alpha, float p_drop, uint64_t seed,
                          void* ws, size_t ws_bytes, void* stream) {
-  if (!d || f < 0 || K < 0 || (dtype != APPNP_F32 && dtype != APPNP_BF16)) return APPNP_EINVAL;
+  if (!d || f < 0 || K < 0 || !appnp::valid_dtype(dtype)) return APPNP_EINVAL;
   if (d->overlap && dtype != APPNP_F32) return APPNP_ENOTSUP;
   if (!(alpha >= 0.0f && alpha <= 1.0f) || !(p_drop >= 0.0f && p_drop < 1.0f))
     return APPNP_EINVAL;
@@ -466,9 +501,8 @@ int appnp_dist_propagate(appnp_dist* d, const void* H, int64_t ld_h, void* Z, in
   const int64_t rows = d->hi - d->lo;
   if (f == 0) return APPNP_OK;
   if (rows > 0 && (!H || !Z || ld_h < f || ld_z < f)) return APPNP_EINVAL;
-  const int64_t es = dtype == APPNP_F32 ? 4 : 2;
   hipStream_t s = as_stream(stream);
-  if (K == 0) return dev_err(copy_rows(Z, ld_z, H, ld_h, rows, f, es, s));
+  if (K == 0) return dev_err(copy_rows(Z, ld_z, H, ld_h, rows, f, appnp::elem_size(dtype), s));
   const WsLayout w = ws_layout(d, f, dtype);
   if (d->sb_requested && !d->split_agreed && dtype == APPNP_F32 && K >= 2) {
     if (!ws || ws_bytes < w.total || ws_bytes < 256 * (size_t)d->nranks) return APPNP_EINVAL;
@@ -481,81 +515,27 @@ int appnp_dist_propagate(appnp_dist* d, const void* H, int64_t ld_h, void* Z, in
   // 16-B vectors is this rank's alone, and it is staged through the workspace ([S, f4] fp32,
   // copied in before the loop and out after it) rather than changing this rank's path (ADVICE
   // r4: round 4 returned APPNP_EINVAL there while the peers waited in the split loop's exchange)
-  if (d->split_ok && w.split_total && K >= 2) {
-    if (!ws || ws_bytes < w.split_total) return APPNP_EINVAL;
-    char* base = static_cast<char*>(ws);
-    const float* h = static_cast<const float*>(H);
-    float* z = static_cast<float*>(Z);
-    int64_t lh = ld_h, lz = ld_z;
-    const bool stage_h = rows > 0 && !aligned16(H, ld_h);
-    const bool stage_z = rows > 0 && !aligned16(Z, ld_z);
-    float* hs = reinterpret_cast<float*>(base + w.stage_off);
-    float* zs = reinterpret_cast<float*>(base + w.stage_off + w.stage_bytes);
-    int rc = APPNP_OK;
-    if (stage_h) {
-      rc = dev_err(copy_rows(hs, w.f4, H, ld_h, rows, f, 4, s));
-      h = hs;
-      lh = w.f4;
-    }
-    if (stage_z) {
-      z = zs;
-      lz = w.f4;
-    }
-    if (rc == APPNP_OK)
-      rc = (d->bcast && w.fs > 0)
-               ? propagate_split_rows_pipelined(d, w, h, lh, z, lz, f, K, alpha, p_drop, seed,
-                                                base, s)
-               : propagate_split_rows(d, w, h, lh, z, lz, f, K, alpha, p_drop, seed, base, s);
-    if (rc == APPNP_OK && stage_z) rc = dev_err(copy_rows(Z, ld_z, zs, w.f4, rows, f, 4, s));
-    return rc;
-  }
-  if (!ws || ws_bytes < w.total) return APPNP_EINVAL;
+  const bool split = d->split_ok && w.split_total && K >= 2;
+  if (!ws || ws_bytes < (split ? w.split_total : w.total)) return APPNP_EINVAL;
+  // the base stays as the caller passes it: every buffer shares its alignment
   char* base = static_cast<char*>(ws);
-  if (d->bcast && dtype == APPNP_F32)
-    return propagate_rows_pipelined(d, w, H, ld_h, Z, ld_z, f, K, alpha, p_drop, seed, base, s);
-  char* buf[2] = {base, base + w.buf_bytes};
-  float* partial = d->overlap ? reinterpret_cast<float*>(base + w.partial_off) : nullptr;
-  const size_t row_bytes = (size_t)(w.ld * es);
-  const size_t shard_bytes = (size_t)d->shard * row_bytes;
-  auto own = [&](char* b) { return b + (size_t)d->lo * row_bytes; };
-
-  // Z_0: the held rows of H, then the whole of it by exchange (synchronous in stream order)
-  int rc = dev_err(copy_rows(own(buf[0]), w.ld, H, ld_h, rows, f, es, s));
-  if (rc == APPNP_OK && d->nranks > 1)
-    rc = exchange_on(d, buf[0], shard_bytes, s);
-  bool pending = false;  // an exchange on xs not yet waited for by `s`
-  for (int k = 0; k < K && rc == APPNP_OK; ++k) {
-    const bool last = k == K - 1;
-    char* src = buf[k & 1];
-    void* dst = last ? Z : static_cast<void*>(own(buf[(k + 1) & 1]));
-    const int64_t ld_dst = last ? ld_z : w.ld;
-    if (d->overlap) {
-      rc = appnp_step(d->g, APPNP_PART_LOCAL, src, w.ld, nullptr, 0, partial, w.ld, nullptr, 0,
-                      f, dtype, k, alpha, p_drop, seed, s);
-      if (rc == APPNP_OK && pending) {
-        rc = dev_err(hipStreamWaitEvent(s, d->exchanged, 0));
-        pending = false;
-      }
-      if (rc == APPNP_OK)
-        rc = appnp_step(d->g, APPNP_PART_REMOTE, src, w.ld, H, ld_h, dst, ld_dst, partial, w.ld,
-                        f, dtype, k, alpha, p_drop, seed, s);
-    } else {
-      rc = appnp_step(d->g, APPNP_PART_ALL, src, w.ld, H, ld_h, dst, ld_dst, nullptr, 0, f,
-                      dtype, k, alpha, p_drop, seed, s);
-    }
-    if (rc != APPNP_OK || last || d->nranks == 1) continue;
-    char* next = buf[(k + 1) & 1];
-    if (d->overlap) {
-      rc = dev_err(hipEventRecord(d->produced, s));
-      if (rc == APPNP_OK) rc = dev_err(hipStreamWaitEvent(d->xs, d->produced, 0));
-      if (rc == APPNP_OK) rc = exchange_on(d, next, shard_bytes, d->xs);
-      if (rc == APPNP_OK) rc = dev_err(hipEventRecord(d->exchanged, d->xs));
-      pending = rc == APPNP_OK;
-    } else {
-      rc = exchange_on(d, next, shard_bytes, s);
-    }
+  Schedule run(d, w, split, base, f, dtype, K, alpha, p_drop, seed, s);
+  run.H = H, run.ld_h = ld_h, run.Z = Z, run.ld_z = ld_z;
+  auto vec16 = [](const void* p, int64_t ld) { return appnp::vec16(&ld, 1, &p, 1); };
+  const bool stage_h = split && rows > 0 && !vec16(H, ld_h);
+  const bool stage_z = split && rows > 0 && !vec16(Z, ld_z);
+  int rc = APPNP_OK;
+  if (stage_h) {
+    run.H = base + w.stage_off;
+    run.ld_h = w.f4;
+    rc = dev_err(copy_rows(base + w.stage_off, w.f4, H, ld_h, rows, f, 4, s));
   }
-  if (pending) (void)hipStreamWaitEvent(s, d->exchanged, 0);  // never leave xs running ahead
+  if (stage_z) {
+    run.Z = base + w.stage_off + w.stage_bytes;
+    run.ld_z = w.f4;
+  }
+  if (rc == APPNP_OK) rc = run.run();
+  if (rc == APPNP_OK && stage_z) rc = dev_err(copy_rows(Z, ld_z, run.Z, w.f4, rows, f, 4, s));
   return rc;
 }
 

@@ -10,6 +10,9 @@
 // tests/golden/capi_trace.txt byte for byte.
 //
 // Run it with every APPNP_* variable removed from the environment (the units cache overrides).
+//
+// dist_trace.cpp, the same for appnp_dist.hip, includes this file with TRACE_STANDINS_ONLY set and
+// so shares the stand-ins and operands, up to the marked line, without this program's cases.
 #include <cinttypes>
 #include <cstdio>
 #include <limits>
@@ -33,6 +36,27 @@ void* new_handle() {
   return at<void>(g_next_handle);
 }
 
+// What dist_trace.cpp turns: by default every stand-in prints its call with every argument and
+// succeeds, and device-to-host copies write nothing.
+bool g_brief = false;   // one short line per call instead of every argument
+int g_launches = 0;     // launches (and 2-D copies) requested so far
+int g_fail_launch = 0;  // the launch (1-based count) that fails; 0: none
+// the byte the device-to-host copy of rank p's agreement flag delivers ("what the peers said")
+const unsigned char* g_peer_flags = nullptr;
+int g_peer_next = 0;
+
+// the end of a launch's line, and what the launch returns
+hipError_t launched() {
+  const bool fails = ++g_launches == g_fail_launch;
+  printf(fails ? " -> fails\n" : "\n");
+  return fails ? hipErrorLaunchFailure : hipSuccess;
+}
+
+// what G(flags) fills, for the builders' stand-ins: the held rows, the local / remote halves when
+// `split` is set, the source-blocked copy for lpe = 1, 2, 4 (0: none)
+void fabricate(appnp_graph* g, int mode, bool split, int lpe, int64_t n, int64_t row_lo,
+               int64_t row_hi);
+
 }  // namespace
 
 // ---- recording stand-ins: the units' imports ----------------------------------------------
@@ -50,6 +74,7 @@ int pick_vec(int dtype, int64_t f, const int64_t* lds, int n_ld, const void* con
       ok = ptrs[i] == nullptr || (reinterpret_cast<uintptr_t>(ptrs[i]) % (uintptr_t)(v * es)) == 0;
     if (ok) break;
   }
+  if (g_brief) return v;
   printf("pick_vec dtype=%d f=%" PRId64 " lds=[", dtype, f);
   for (int i = 0; i < n_ld; ++i) printf("%s%" PRId64, i ? "," : "", lds[i]);
   printf("] ptrs=[");
@@ -73,30 +98,42 @@ static void print_args(const StepArgs& a) {
 }
 
 hipError_t launch_step(int dtype, int epi, int V, const StepArgs& a, hipStream_t s) {
+  if (g_brief) {
+    printf("step s=%#llx epi=%d rows=%#llx:%#llx zin=%#llx out=%#llx aux=%#llx", X(s), epi,
+           X(a.row_ptr), X(a.row_end), X(a.zin), X(a.out), X(a.aux));
+    return launched();
+  }
   printf("launch_step dtype=%d epi=%d V=%d s=%#llx", dtype, epi, V, X(s));
   print_args(a);
-  printf("\n");
-  return hipSuccess;
+  return launched();
 }
 
 hipError_t launch_remainder(const appnp_graph* g, const StepArgs& a, int epi, const float* z_rem,
                             const float* h_rem, int64_t ld_h, float* out, int64_t ld_out, int nv,
                             bool to_rem, hipStream_t s) {
+  if (g_brief) {
+    printf("remainder s=%#llx z_rem=%#llx out=%#llx to_rem=%d", X(s), X(z_rem), X(out),
+           (int)to_rem);
+    return launched();
+  }
   printf("launch_remainder lpe=%d epi=%d z_rem=%#llx h_rem=%#llx ld_h=%" PRId64
          " out=%#llx ld_out=%" PRId64 " nv=%d to_rem=%d s=%#llx",
          g->rb_lpe, epi, X(z_rem), X(h_rem), ld_h, X(out), ld_out, nv, (int)to_rem, X(s));
   print_args(a);
-  printf("\n");
-  return hipSuccess;
+  return launched();
 }
 
 hipError_t launch_split_copy(const float* h, int64_t ld_h, int64_t n, int64_t f, int64_t fs,
                              int64_t rw, float* main, float* rem, const float* rem_scale,
                              hipStream_t s) {
+  if (g_brief) {
+    printf("split_copy s=%#llx main=%#llx rem=%#llx", X(s), X(main), X(rem));
+    return launched();
+  }
   printf("launch_split_copy h=%#llx ld_h=%" PRId64 " n=%" PRId64 " f=%" PRId64 " fs=%" PRId64
-         " rw=%" PRId64 " main=%#llx rem=%#llx rem_scale=%#llx s=%#llx\n",
+         " rw=%" PRId64 " main=%#llx rem=%#llx rem_scale=%#llx s=%#llx",
          X(h), ld_h, n, f, fs, rw, X(main), X(rem), X(rem_scale), X(s));
-  return hipSuccess;
+  return launched();
 }
 
 hipError_t launch_scale_rows(int dtype, const void* src, int64_t ld_src, void* dst,
@@ -136,7 +173,9 @@ hipError_t launch_poly_reduce(const float* part, int64_t count, float* out, hipS
   return hipSuccess;
 }
 
-int g_build_rc = APPNP_OK;  // what the graph_build* stand-ins return
+int g_build_rc = APPNP_OK;  // what the graph_build_source_blocks stand-in returns
+
+// The builders fabricate what they are asked for, as G(flags) does.
 
 int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals, int64_t n,
                 int64_t nnz, int mode, int64_t row_lo, int64_t row_hi, int split, hipStream_t s,
@@ -144,7 +183,7 @@ int graph_build(const int32_t* indptr, const int32_t* indices, const float* vals
   printf("graph_build indptr=%#llx indices=%#llx vals=%#llx n=%" PRId64 " nnz=%" PRId64
          " mode=%d row_lo=%" PRId64 " row_hi=%" PRId64 " split=%d s=%#llx\n",
          X(indptr), X(indices), X(vals), n, nnz, mode, row_lo, row_hi, split, X(s));
-  g->mode = mode;
+  fabricate(g, mode, split != 0, 0, n, row_lo, row_hi);
   return APPNP_OK;
 }
 
@@ -153,17 +192,22 @@ int graph_build_transpose(appnp_graph*, hipStream_t s) {
   return APPNP_OK;
 }
 
-int graph_build_source_blocks(appnp_graph*, int lpe, const int32_t* a_indptr,
+int graph_build_source_blocks(appnp_graph* g, int lpe, const int32_t* a_indptr,
                               const int32_t* a_indices, int64_t a_nnz, hipStream_t s) {
   printf("graph_build_source_blocks lpe=%d a_indptr=%#llx a_indices=%#llx a_nnz=%" PRId64
          " s=%#llx -> %d\n",
          lpe, X(a_indptr), X(a_indices), a_nnz, X(s), g_build_rc);
+  if (g_build_rc == APPNP_OK)
+    fabricate(g, g->mode, g->split != 0, lpe, g->n, g->row_lo, g->row_hi);
   return g_build_rc;
 }
 
-int graph_build_shard_offsets(appnp_graph*, int nshards, int64_t shard_rows, hipStream_t s) {
+int graph_build_shard_offsets(appnp_graph* g, int nshards, int64_t shard_rows, hipStream_t s) {
   printf("graph_build_shard_offsets nshards=%d shard_rows=%" PRId64 " s=%#llx\n", nshards,
          shard_rows, X(s));
+  g->sh_off = at<int32_t>(0x19000000);
+  g->sh_n = nshards;
+  g->sh_rows = shard_rows;
   return APPNP_OK;
 }
 
@@ -178,12 +222,17 @@ hipError_t hipEventCreate(hipEvent_t* e) {
   printf("hipEventCreate -> %#llx\n", X(*e));
   return hipSuccess;
 }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned int flags) {
+  *e = static_cast<hipEvent_t>(new_handle());
+  printf("hipEventCreateWithFlags flags=%u -> %#llx\n", flags, X(*e));
+  return hipSuccess;
+}
 hipError_t hipEventDestroy(hipEvent_t e) {
   printf("hipEventDestroy %#llx\n", X(e));
   return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
-  printf("hipEventRecord %#llx s=%#llx\n", X(e), X(s));
+  printf(g_brief ? "record %#llx s=%#llx\n" : "hipEventRecord %#llx s=%#llx\n", X(e), X(s));
   return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
@@ -197,15 +246,31 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
 }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind,
                           hipStream_t s) {
+  if (g_peer_flags && kind == hipMemcpyDeviceToHost && bytes == 1) {
+    // the agreement reads rank p's flag into host memory: the address is the run's, not printed
+    const unsigned char v = g_peer_flags[g_peer_next++];
+    *static_cast<unsigned char*>(dst) = v;
+    printf("hipMemcpyAsync dst=host src=%#llx bytes=1 kind=%d s=%#llx -> %d\n", X(src), (int)kind,
+           X(s), (int)v);
+    return hipSuccess;
+  }
   printf("hipMemcpyAsync dst=%#llx src=%#llx bytes=%zu kind=%d s=%#llx\n", X(dst), X(src), bytes,
          (int)kind, X(s));
   return hipSuccess;
 }
 hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch,
                             size_t width, size_t height, hipMemcpyKind kind, hipStream_t s) {
+  if (g_brief) {
+    printf("copy2d s=%#llx dst=%#llx src=%#llx", X(s), X(dst), X(src));
+    return launched();
+  }
   printf("hipMemcpy2DAsync dst=%#llx dpitch=%zu src=%#llx spitch=%zu width=%zu height=%zu kind=%d"
-         " s=%#llx\n",
+         " s=%#llx",
          X(dst), dpitch, X(src), spitch, width, height, (int)kind, X(s));
+  return launched();
+}
+hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t s) {
+  printf("hipMemsetAsync dst=%#llx value=%d bytes=%zu s=%#llx\n", X(dst), value, bytes, X(s));
   return hipSuccess;
 }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int flags) {
@@ -215,6 +280,17 @@ hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int flags) {
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
   printf("hipStreamDestroy %#llx\n", X(s));
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) {
+  printf("hipStreamSynchronize %#llx\n", X(s));
+  return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned int flags) {
+  if (g_brief)
+    printf("wait s=%#llx %#llx\n", X(s), X(e));
+  else
+    printf("hipStreamWaitEvent s=%#llx %#llx flags=%u\n", X(s), X(e), flags);
   return hipSuccess;
 }
 hipError_t hipStreamBeginCapture(hipStream_t s, hipStreamCaptureMode mode) {
@@ -265,14 +341,11 @@ enum : unsigned {
   G_EMPTY = 0x1000,  // holds no row
 };
 
-std::vector<std::unique_ptr<appnp_graph>> g_graphs;  // of the running case
-
-appnp_graph* G(unsigned fl) {
-  g_graphs.emplace_back(new appnp_graph());
-  appnp_graph* g = g_graphs.back().get();
-  g->n = (fl & G_SMALL) ? 1000 : 200000;
-  g->row_lo = (fl & (G_ROWS | G_EMPTY)) ? g->n / 4 : 0;
-  g->row_hi = (fl & G_EMPTY) ? g->row_lo : (fl & G_ROWS) ? 3 * g->n / 4 : g->n;
+// rows [row_lo, row_hi) of an n-node graph with the parts `fl` names
+void fill(appnp_graph* g, unsigned fl, int64_t n, int64_t row_lo, int64_t row_hi) {
+  g->n = n;
+  g->row_lo = row_lo;
+  g->row_hi = row_hi;
   g->nnz_hat = 25 * (g->row_hi - g->row_lo) + 3;
   g->mode = (fl & G_RW) ? APPNP_NORM_RW : APPNP_NORM_SYM;
   g->symmetric = (fl & G_ASYM) ? 0 : 1;
@@ -330,23 +403,47 @@ appnp_graph* G(unsigned fl) {
     g->sh_rows = (g->n + 2) / 3;
   }
   g->near_frac = (fl & G_NEAR) ? 0.9 : 0.013;
-  return g;
+}
+
+void fabricate(appnp_graph* g, int mode, bool split, int lpe, int64_t n, int64_t row_lo,
+               int64_t row_hi) {
+  fill(g, (mode == APPNP_NORM_RW ? G_RW : 0u) | (split ? G_SPLIT : 0u) |
+              (lpe == 4 ? G_SB16 : lpe == 2 ? G_SB8 : lpe == 1 ? G_SB4 : 0u),
+       n, row_lo, row_hi);
 }
 
 void* const kH = at<void>(0x20000000);
 void* const kZ = at<void>(0x30000000);
 void* const kWs = at<void>(0x40000000);
-float* const kPartial = at<float>(0x50000000);
-float* const kZinMain = at<float>(0x60000000);
-float* const kZinRem = at<float>(0x61000000);
-float* const kZoutMain = at<float>(0x62000000);
-float* const kZoutRem = at<float>(0x63000000);
 void* const kStream = at<void>(0x5ee0);
 
 template <typename T>
 T* off(T* p, intptr_t bytes) {
   return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes);
 }
+
+}  // namespace
+
+#ifndef TRACE_STANDINS_ONLY  // dist_trace.cpp includes what is above; the rest is this program's
+
+namespace {
+
+std::vector<std::unique_ptr<appnp_graph>> g_graphs;  // of the running case
+
+appnp_graph* G(unsigned fl) {
+  g_graphs.emplace_back(new appnp_graph());
+  appnp_graph* g = g_graphs.back().get();
+  const int64_t n = (fl & G_SMALL) ? 1000 : 200000;
+  const int64_t lo = (fl & (G_ROWS | G_EMPTY)) ? n / 4 : 0;
+  fill(g, fl, n, lo, (fl & G_EMPTY) ? lo : (fl & G_ROWS) ? 3 * n / 4 : n);
+  return g;
+}
+
+float* const kPartial = at<float>(0x50000000);
+float* const kZinMain = at<float>(0x60000000);
+float* const kZinRem = at<float>(0x61000000);
+float* const kZoutMain = at<float>(0x62000000);
+float* const kZoutRem = at<float>(0x63000000);
 
 // appnp_propagate / _bwd / appnp_solve / _bwd / appnp_plan_create(_solve): H, Z are dZ, dH in
 // the adjoints; K is `iters` in the solver
@@ -1257,3 +1354,5 @@ int main() {
   }
   return 0;
 }
+
+#endif  // TRACE_STANDINS_ONLY

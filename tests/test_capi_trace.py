@@ -9,6 +9,8 @@ tests/golden/capi_trace.txt byte for byte: the file was recorded before the orch
 folded onto shared helpers and is the proof that a change to the units requests the same launches
 (the appnp_poly cases were recorded before the propagation calls got a unit of their own).
 A change that is meant to alter a launch regenerates the file and shows the difference in review.
+The row-partition engine (appnp_dist.hip) is pinned the same way by the sibling test_dist_trace.py;
+the two programs share the stand-ins of capi_trace.cpp.
 """
 
 import os
